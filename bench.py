@@ -7,7 +7,11 @@ reference's driver loop (hsr/control.py:73-75) and, for N > 1, one RCCL all-gath
 Workload (config.workload): BASELINE config 3 - all 7 DOFs + 1 block, 8192 envs per GPU (weak scaling),
 synthetic inputs of SURVEY.md section 8d resident in HBM before the timed region.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K env-steps and prints one JSON line (headline figure, ms_per_step, workload).
+--full adds everything else the benchmark measures: workload statistics of the timed steps (substeps, dones, cap hits, bad
+envs), per-launch kernel times and the roofline report, the secondary `capacity` leg and the CPU baseline.
+--dump-outputs DIR writes what the last timed env-step handed its caller as DIR/<name>.npy (float32).
 N > 1 works both ways: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE in
 the environment) and as the plain command above, which then starts the N ranks itself (one child process per GPU; the parent
 never touches the GPU) and relays rank 0's JSON line.
@@ -144,6 +148,25 @@ def capacity_leg(m, n, dev, device_id, K=3, W=2):
             "note": "secondary: throughput of ONE GPU at saturation (same workload, more envs per GPU, work queue); not the BASELINE configuration, never the headline"}
 
 
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, offset=0, **arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array (rows = envs).  Beyond DUMP_BYTES in all, a fixed, seeded sample of rows is
+    kept - the same envs in every run of the same arguments - and their global env ids go to env_index.npy."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.asarray(a, dtype=np.float32) for k, a in arrays.items()}
+    rows = len(next(iter(arrays.values())))
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    if rows * row_bytes > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(rows, DUMP_BYTES // (row_bytes + 8), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        np.save(d / "env_index.npy", (keep + offset).astype(np.float64))
+    for k, a in arrays.items():
+        np.save(d / f"{k}.npy", np.ascontiguousarray(a))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: start N ranks of this script (env:// rendezvous on 127.0.0.1), relay rank
     0's output, fail if any rank fails.  Runs before torch / HIP are touched - the parent process never initialises the GPU.
@@ -216,11 +239,20 @@ def main():
                     "multi-GPU run would own); inputs are keyed by global env id, so the shard is reproduced env for env")
     ap.add_argument("--dump-step", default=None, help="rank 0 writes obs | reward | done of the LAST timed env-step to this .npy: the gathered "
                     "[global_envs, nq+nv+2] buffer for N > 1, the local one otherwise (tests compare the two)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the LAST timed env-step handed its caller as "
+                    "DIR/<name>.npy in float32: obs, reward, done (the gathered global arrays for N > 1) and, for N = 1, nsteps (substeps run); "
+                    "inputs are seeded, so two builds can be compared output for output.  Beyond 64 MB in all a fixed, seeded sample of "
+                    "envs is written, with their global ids in env_index.npy")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: workload statistics of the "
+                    "timed steps, per-launch kernel times and the roofline report, the `capacity` leg and the CPU baseline (a plain run "
+                    "does only set-up, warm-up, the timed steps, --dump-outputs and the result line)")
     ap.add_argument("--launch-check", action="store_true", help="print this rank's rendezvous environment and exit (no GPU touched): "
                     "exercises the self-launcher of --gpus N on a machine without GPUs")
     ap.add_argument("--fail-rank", type=int, default=-1, help="with --launch-check: this rank exits with code 3 at once and the others "
                     "wait (as a rank does whose peer never reaches the rendezvous) - the launcher has to take them down")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
     if args.launch_check:
@@ -304,9 +336,10 @@ def main():
     for k in range(W):
         env_step(k)
     barrier()
-    sim.cap_counts()                        # clears the counters: the cap statistics below cover the timed steps only
-    sim.set_profiling(2)                    # an event pair around every launch of the persistent kernel, no synchronisation
-    barrier()
+    if args.full:
+        sim.cap_counts()                    # clears the counters: the cap statistics below cover the timed steps only
+        sim.set_profiling(2)                # an event pair around every launch of the persistent kernel, no synchronisation
+        barrier()
     t0 = time.perf_counter()
     for k in range(W, W + K):
         env_step(k)
@@ -316,11 +349,47 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if args.rehearse_on_one_gpu else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if not args.full:
+        sim.sync()                          # raises if a launch of the timed region was drained by the work queue's watchdog (--full: kernel_times below)
     if args.dump_step and rank == 0:
         if last_gathered[0] is not None:
             np.save(args.dump_step, last_gathered[0].detach().cpu().numpy())
         else:
             np.save(args.dump_step, np.concatenate([d_obs.cpu().numpy(), d_rew.cpu().numpy()[:, None], d_done[W + K - 1].cpu().numpy()[:, None].astype(np.float32)], axis=1))
+    if args.dump_outputs and rank == 0:
+        if last_gathered[0] is not None:
+            g = last_gathered[0].detach().cpu().numpy()
+            dump_outputs(args.dump_outputs, obs=g[:, :nobs], reward=g[:, nobs], done=g[:, nobs + 1])
+        else:
+            dump_outputs(args.dump_outputs, offset=offset, obs=d_obs.cpu().numpy(), reward=d_rew.cpu().numpy(),
+                         done=d_done[W + K - 1].cpu().numpy(), nsteps=d_ns[W + K - 1].cpu().numpy())
+
+    value = world * n * K / dt
+    nblocks = len(m.free_joint_qadrs())
+    dofs = {2: "slide_x/slide_y DOFs only", 7: "all 7 DOFs"}.get(m.nu, f"{m.nu} actuated DOFs")
+    baseline_cfg = {"cfg1": "BASELINE config 1 shape", "cfg2": "BASELINE config 2", "cfg3": "BASELINE config 3",
+                    "cfg4": "BASELINE configs 4/5 per-GPU shard"}.get(args.config, "SURVEY 8f scene")
+    out = {
+        "metric": f"env-steps/sec (whole node), HSR+{nblocks}-block, steps_per_action={STEPS_PER_ACTION}, {n} envs",
+        "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
+        "ms_per_step": 1e3 * dt / K, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{baseline_cfg}: {args.config}, {dofs} + {nblocks} block(s), {n} envs per GPU x {world} GPU(s), "
+                               f"steps_per_action={STEPS_PER_ACTION}, geofence={GEOFENCE}, ctrl~U(ctrlrange) per env-step, done envs reset",
+                   "envs_per_gpu": n, "global_envs": world * n, "substeps_per_env_step": STEPS_PER_ACTION,
+                   "gather_mode": (None if world == 1 else ("overlapped with the next env-step (open loop)" if gather_overlap else "in line (closed loop)")),
+                   "parallelism": f"env-shard x{world}" + (f" + all-gather(obs,reward,done) over {'gloo (rehearsal)' if args.rehearse_on_one_gpu else 'RCCL'}, {dist.get_world_size()} ranks{', overlapped with the next env-step' if gather_overlap else ''}" if world > 1 else ""),
+                   "persistent_kernel": persistent, "hipgraph": (not args.no_graph) and not persistent},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        sim.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # --full: what the timed steps did, per-launch kernel times, the roofline report, the capacity leg and the CPU baseline
     substeps_done = int(d_ns[W:W + K].sum().item())
     dones = int(d_done[W:W + K].sum().item())
 
@@ -367,13 +436,8 @@ def main():
                                   "not collected in this run): " + str(pj.get("_note", ""))[:160])
         except Exception:
             traffic = None
-    value = world * n * K / dt
     bad, any_bad = sim.bad_state()
     cap_con, cap_row, cap_item, cap_total = sim.cap_counts()
-    nblocks = len(m.free_joint_qadrs())
-    dofs = {2: "slide_x/slide_y DOFs only", 7: "all 7 DOFs"}.get(m.nu, f"{m.nu} actuated DOFs")
-    baseline_cfg = {"cfg1": "BASELINE config 1 shape", "cfg2": "BASELINE config 2", "cfg3": "BASELINE config 3",
-                    "cfg4": "BASELINE configs 4/5 per-GPU shard"}.get(args.config, "SURVEY 8f scene")
     # the roofline that binds: FP32 VALU issue.  Wave-instructions per wave per substep come from the committed
     # PMC pass of this kernel (profiles/pmc_summary.json, SQ_INSTS_VALU); peak = 1024 SIMD-32 x 2.4 GHz / 2 clocks per wave64 op
     valu = None
@@ -399,22 +463,14 @@ def main():
     except Exception:
         lifetimes = None
 
-    out = {
-        "metric": f"env-steps/sec (whole node), HSR+{nblocks}-block, steps_per_action={STEPS_PER_ACTION}, {n} envs",
-        "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
-        "ms_per_step": 1e3 * dt / K, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{baseline_cfg}: {args.config}, {dofs} + {nblocks} block(s), {n} envs per GPU x {world} GPU(s), "
-                               f"steps_per_action={STEPS_PER_ACTION}, geofence={GEOFENCE}, ctrl~U(ctrlrange) per env-step, done envs reset",
-                   "envs_per_gpu": n, "global_envs": world * n, "substeps_per_env_step": STEPS_PER_ACTION,
+    out["config"].update({
                    "mean_substeps_executed": mean_substeps, "done_fraction": dones / (n * K),
-                   "gather_mode": (None if world == 1 else ("overlapped with the next env-step (open loop)" if gather_overlap else "in line (closed loop)")),
-                   "parallelism": f"env-shard x{world}" + (f" + all-gather(obs,reward,done) over {'gloo (rehearsal)' if args.rehearse_on_one_gpu else 'RCCL'}, {dist.get_world_size()} ranks{', overlapped with the next env-step' if gather_overlap else ''}" if world > 1 else ""),
                    "cap_hits": {"contacts_beyond_nconmax": cap_con / max(cap_total, 1), "rows_beyond_njmax": cap_row / max(cap_total, 1),
                                 "items_beyond_64_per_env": cap_item / max(cap_total, 1), "env_substeps": cap_total,
                                 "nconmax_njmax": [int(m.arrays["sizes"][10]), int(m.arrays["sizes"][11])], "note": "fraction of (env, substep) pairs; MuJoCo's own caps are 100 / 500 (world.xml:44)"},
-                   "substeps_per_s": value * mean_substeps, "persistent_kernel": persistent, "hipgraph": (not args.no_graph) and not persistent,
-                   "bad_envs": int(bad.sum())},
+                   "substeps_per_s": value * mean_substeps,
+                   "bad_envs": int(bad.sum())})
+    out.update({
         # bound / achieved / peak / unit / frac / traffic belong together: the HBM report BASELINE prescribes (round-5 advisor: a "valu" bound next to an
         # HBM fraction misleads a consumer that reads the two together); what actually binds - FP32 VALU issue / latency - is `binding` + `valu`
         "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -426,7 +482,7 @@ def main():
                      "kernel_ms_per_env_step": {nm: ms for nm, ms in zip(names, k_ms) if nm != "-"},
                      "launches_per_env_step": {nm: k for nm, k in zip(names, k_n) if nm != "-"},
                      "note": "state stays L2/MALL-resident; the path is FP32-VALU/latency bound, not HBM bound (SURVEY.md 8d)"},
-    }
+    })
     if world == 1 and persistent and not args.no_capacity and args.capacity_envs > n:
         out["capacity"] = capacity_leg(m, args.capacity_envs, dev, local_rank)
     if rank == 0 and not args.no_cpu_baseline:

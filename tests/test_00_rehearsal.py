@@ -31,7 +31,7 @@ def test_two_ranks_on_one_gpu_reproduce_the_single_process_shards(tmp_path, cfg)
     and the reset of finished envs in one process pair."""
     two = tmp_path / "two.npy"
     common = ["--config", cfg, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-capacity"]
-    line = _bench(["--gpus", "2", "--rehearse-on-one-gpu"] + common + ["--dump-step", str(two)])
+    line = _bench(["--gpus", "2", "--rehearse-on-one-gpu", "--full"] + common + ["--dump-step", str(two)])
     assert cfg in line["config"]["workload"] and line["config"]["gather_mode"] == "in line (closed loop)"
     assert line["n_gpus"] == 2 and line["steps"] == 2 and line["warmup"] == 1 and line["scaling"] == "weak"
     assert line["config"]["global_envs"] == 16384 and line["config"]["envs_per_gpu"] == 8192
@@ -41,12 +41,19 @@ def test_two_ranks_on_one_gpu_reproduce_the_single_process_shards(tmp_path, cfg)
     g = np.load(two)
     nobs = g.shape[1] - 2
     assert g.shape[0] == 16384 and np.isfinite(g).all()
-    # each rank's rows of the gathered buffer == a one-rank run of the same global env ids (inputs are keyed by the shard's offset)
+    # each rank's rows of the gathered buffer == a one-rank run of the same global env ids (inputs are keyed by the shard's offset);
+    # these runs are plain ones (no --full), and their --dump-outputs arrays are the columns of the --dump-step buffer
     for r in (0, 1):
         one = tmp_path / f"one{r}.npy"
-        l1 = _bench(["--gpus", "1"] + common + ["--env-offset", str(8192 * r), "--dump-step", str(one)])
+        outs = tmp_path / f"outputs{r}"
+        l1 = _bench(["--gpus", "1"] + common + ["--env-offset", str(8192 * r), "--dump-step", str(one), "--dump-outputs", str(outs)])
         assert l1["config"]["gather_mode"] is None
         assert l1["n_gpus"] == 1 and l1["config"]["global_envs"] == 8192
+        assert l1["steps"] == 2 and l1["ms_per_step"] > 0 and "roofline" not in l1 and "cpu_baseline" not in l1
         o = np.load(one)
         assert o.shape == (8192, nobs + 2)
         assert np.array_equal(g[8192 * r:8192 * (r + 1)], o), f"rank {r}'s shard of the gathered step differs from the single-process run of the same envs"
+        d = {k: np.load(outs / f"{k}.npy") for k in ("obs", "reward", "done", "nsteps")}
+        assert all(a.dtype == np.float32 for a in d.values()) and not (outs / "env_index.npy").exists()
+        assert np.array_equal(d["obs"], o[:, :nobs]) and np.array_equal(d["reward"], o[:, nobs]) and np.array_equal(d["done"], o[:, nobs + 1])
+        assert d["nsteps"].shape == (8192,) and ((d["nsteps"] >= 0) & (d["nsteps"] <= 300)).all()

@@ -6,6 +6,9 @@ import pytest
 
 from hsr_env_amd import compiler as hc
 
+# the reference's MJCF scenes and STL meshes, stored verbatim: what the model compiler reads
+REF_DATA = Path(__file__).parent / "golden" / "hsr_data"
+
 # cfg: nq nv nu obs nbody collidable-geoms candidate-pairs   
 TABLE = {"cfg1": (2, 2, 2, 4, 47, 17, 30), "cfg2": (9, 8, 2, 17, 48, 18, 47),
          "cfg3": (14, 13, 7, 27, 48, 18, 114), "cfg4": (28, 25, 7, 53, 50, 20, 151),
@@ -61,10 +64,9 @@ def test_pair_filters(models):
     assert (m.geom_type[m.pair_geom1] <= m.geom_type[m.pair_geom2]).all()
 
 
-@pytest.mark.skipif(not hc.DEFAULT_REF_ROOT.exists(), reason="reference data files not on this machine")
 @pytest.mark.parametrize("cfg", ["cfg1", "cfg3"])
 def test_recompile_matches_committed_blob(models, cfg):
-    fresh = hc.compile_model(**hc.CONFIGS[cfg])
+    fresh = hc.compile_model(**hc.CONFIGS[cfg], ref_root=REF_DATA)
     for k, a in models[cfg].arrays.items():
         assert np.allclose(a, fresh.arrays[k], rtol=1e-12, atol=1e-14), k
 

@@ -146,12 +146,14 @@ def test_init_demo_shape_runs_on_the_cupboard_scene(models):
     assert np.allclose(env.block_pos(), env.sim.body_xpos(m.body_id("block")))
 
 
-def test_cli_set_xml_and_xml_file(models):
+def test_cli_set_xml_and_xml_file(models, monkeypatch, tmp_path):
     """hsr/util.py:36-37,43-44,129-135: `--xml-file`, `--set-xml path,value` (last path component = attribute, the rest an
     ElementTree path in whichever file it matches).  A known config resolves to its committed blob; a setter needs the
-    model compiler and the MJCF / STL data files."""
+    model compiler and the MJCF / STL data files (the stored copies under tests/golden/hsr_data stand in for them)."""
     import argparse
-    from hsr_env_amd.compiler import DEFAULT_REF_ROOT
+    import functools
+    from pathlib import Path
+    from hsr_env_amd import compiler as hc
     parser = argparse.ArgumentParser()
     util.add_env_args(parser.add_argument_group("env_args")); util.add_wrapper_args(parser.add_argument_group("wrapper_args"))
     args = util.hierarchical_parse_args(parser, ["--steps-per-action=300", "--geofence=.05", "--goal-space", "(0,0)(0,0)(.498,.498)",
@@ -162,10 +164,13 @@ def test_cli_set_xml_and_xml_file(models):
     assert w["set_xml"] == [util.XMLSetter("option/timestep", "0.001"), util.XMLSetter("body/joint[@name='slide_x']/damping", "1000")]
     m = util.model_for(w["use_dof"], w["n_blocks"], w["xml_file"])
     assert m.to_bytes() == models["cupboard"].to_bytes()
-    if not DEFAULT_REF_ROOT.exists():
-        with pytest.raises(IOError):
-            util.model_for(w["use_dof"], w["n_blocks"], w["xml_file"], w["set_xml"])
-        return
+    # without the data files a setter is an IOError
+    monkeypatch.setattr(util, "DEFAULT_REF_ROOT", tmp_path / "missing")
+    with pytest.raises(IOError):
+        util.model_for(w["use_dof"], w["n_blocks"], w["xml_file"], w["set_xml"])
+    ref_data = Path(__file__).parent / "golden" / "hsr_data"
+    monkeypatch.setattr(util, "DEFAULT_REF_ROOT", ref_data)
+    monkeypatch.setattr(util, "compile_model", functools.partial(hc.compile_model, ref_root=ref_data))
     m2 = util.model_for(w["use_dof"], w["n_blocks"], w["xml_file"], w["set_xml"])
     assert m2.timestep == 0.001 and m2.meta["set_xml"][0] == ["option/timestep", "0.001"]
     i = m2.meta["dofs"].index("slide_x")

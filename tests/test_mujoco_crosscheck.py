@@ -1,5 +1,5 @@
 """External pin of the oracle: when a real MuJoCo is importable (`mujoco`, or the reference's own
-`mujoco_py`) AND the reference's data files are on disk, the MJCF that hsr/util.py:mutate_xml would produce for each
+`mujoco_py`) AND the reference's data files are on disk (tests/golden/hsr_data), the MJCF that hsr/util.py:mutate_xml would produce for each
 configuration (hsr_env_amd.compiler.emit_mjcf) is loaded into it, the golden rollouts' inputs are replayed, and the oracle's
 committed trajectories must follow MuJoCo's per substep.  Neither is available in the build container or on the GPU box, so this
 file normally SKIPS; run it wherever MuJoCo lives, with HSR_WRITE_MUJOCO_GOLDEN=1 to also write tests/golden/mujoco_<cfg>.npz,
@@ -16,6 +16,7 @@ import pytest
 from hsr_env_amd import compiler as hc
 
 GOLD = Path(__file__).parent / "golden"
+REF_DATA = GOLD / "hsr_data"          # the reference's MJCF scenes and STL meshes, stored verbatim
 
 
 def _engine():
@@ -33,7 +34,7 @@ def _engine():
 
 KIND, ENGINE = _engine()
 pytestmark = [pytest.mark.skipif(ENGINE is None, reason="no MuJoCo (mujoco / mujoco_py) importable"),
-              pytest.mark.skipif(not hc.DEFAULT_REF_ROOT.exists(), reason="reference MJCF / STL data files not on disk")]
+              pytest.mark.skipif(not REF_DATA.exists(), reason="reference MJCF / STL data files not on disk")]
 
 
 def _rollout(xml, names, q0, ctrl, nsub):
@@ -70,7 +71,7 @@ def test_oracle_follows_mujoco(models, cfg, tmp_path):
     g = np.load(GOLD / f"golden_{cfg}.npz")
     m = models[cfg]
     kw = dict(hc.CONFIGS[cfg])
-    xml = hc.emit_mjcf(tmp_path, cfg, **kw)
+    xml = hc.emit_mjcf(tmp_path, cfg, ref_root=REF_DATA, **kw)
     names = [n for n in m.names["joint"] if n]
     nsub = g["qpos"].shape[1]
     Q, V, C, version = _rollout(xml, names, g["qpos0"], g["ctrl"], nsub)
