@@ -216,6 +216,7 @@ extern "C" int hsr_model_joint_qpos_addr(const hsr_model *m, const char *name, i
 }
 
 // ------------------------------------------------------------------ batch
+typedef void (*persist_fn)(const DevModel *, DevState, int, int, float, int, StepIO);
 struct GraphKey { int nsub, goal_body; float geofence; bool operator<(const GraphKey &o) const { return std::tie(nsub, goal_body, geofence) < std::tie(o.nsub, o.goal_body, o.geofence); } };
 
 struct hsr_batch {
@@ -234,11 +235,16 @@ struct hsr_batch {
     int narrow_blocks = 2048;      // persistent-style grid of k_narrow (HSR_NARROW_BLOCKS overrides)
     int pairs_per_wave = 4;        // k_collide: pairs walked by one wave (HSR_PPW overrides)
     int group = 16;                // lanes per env of the cooperative solver
-    size_t mf_lds_bytes = 0, persist_lds_bytes = 0;
-    bool persist = false;          // whole env-step in one persistent kernel (k_env_step_mf); HSR_PERSIST=0 disables
-    bool persist_ok = false;       // the model fits the persistent kernel (lane maps, LDS, kinematic structure): set once at creation
+    size_t mf_lds_bytes = 0;
+    bool persist = false;          // whole env-step in one persistent kernel (k_env_step_mf); hsr_batch_set_persistent(b, 0) disables
     bool use_graph = true, profiling = false, debug_store = false;
-    bool persist_tg = false;       // persistent kernel instance that reads its pair / geom tables from global memory (LDS budget)
+    // the persistent-kernel instance, chosen once at creation (plan_persist) and read by every later use
+    int const_row = -1;            // row of kCfgConsts (cfg_consts.h) whose constant instance serves the model, -1 = a generic instance
+    bool kin3 = false;             // ... and that instance knows the model's kinematic tree at compile time (kin3.h)
+    bool persist_tg = false;       // the instance reads its pair / geom tables from global memory (LDS budget)
+    persist_fn kernel = nullptr;   // the instance; NULL: the model does not fit the persistent kernel (lane maps, LDS, kinematic structure)
+    persist_fn kernel_sv = nullptr;     // its twin with the solo-server path, NULL if there is none
+    size_t persist_lds_bytes = 0;
     bool mpr_warm = true;          // penetrating convex pairs start MPR from the portal of their previous substep (HSR_MPR_WARM=0 / hsr_batch_set_mpr_warm turn it off)
     int test_hooks = 0;            // hsr_batch_set_debug bits 1.. : force rarely taken solver branches (tests only)
     bool schedule = true;          // re-pack the envs over the waves of the persistent kernel before every launch (HSR_SCHEDULE=0 / hsr_batch_set_schedule turn it off)
@@ -254,7 +260,6 @@ struct hsr_batch {
     bool queue_chunk_set = false;  // ... chosen by the caller (environment / hsr_batch_set_queue): no automatic choice then
     int solo_servers = 0;          // workgroups of a queued launch that run hard envs alone (persist.h; hsr_batch_set_solo / HSR_SOLO); 0 = off
     float solo_trips = 3.5f;       // hand-over threshold: Newton iterations per substep over a round
-    bool solo_ok = false;          // the chosen kernel instance has the server path
     bool kernel_log = false;       // hsr_batch_set_profiling(b, 2): an event pair around every launch of the persistent kernel, no synchronisation
     std::vector<std::pair<hipEvent_t, hipEvent_t>> klog;
 };
@@ -274,89 +279,66 @@ __global__ void k_build_tables(DevModel m, DevState s) {
     }
 }
 
-// The persistent kernel instantiations.  Every reference configuration has an instance with ALL scalar model fields at compile time
+// The persistent kernel instances.  Every reference configuration has an instance with ALL scalar model fields at compile time
 // (cfg_consts.h, generated from the committed blobs; chosen only when the loaded model matches the generated row value for value -
-// HSR_NO_CONST=1 never chooses them); any other model runs a generic instance (lanes per env, bound on nv).
-typedef void (*persist_fn)(const DevModel *, DevState, int, int, float, int, StepIO);
-static void quat2mat_h(const double *q, float *mt);
-// row + 1 of the constant instance whose compile-time tree tables (cfg_consts.h: Kin3_<cfg>) equal the loaded model's, 0 if none: the order of
-// the entries is the one tools/gen_cfg_consts.py writes
-static int kin3_matching_row(const hsr_model *m) {
-    const int nv = m->sizes[1], nlink = m->sizes[3];
-    std::vector<int> iv = {nlink, nv};
-    for (const char *n : {"link_parent", "link_free", "link_dofadr", "link_dofnum", "link_qposadr", "dof_type", "dof_qposadr", "dof_link"}) {
-        size_t cnt = 0; const int *p = m->i32(n, &cnt);
-        if (!p) return 0;
-        iv.insert(iv.end(), p, p + cnt);
-    }
-    std::vector<float> fv;
-    auto addf = [&](const char *n) { size_t cnt = 0; const double *p = m->f64(n, &cnt); if (!p) return false; for (size_t i = 0; i < cnt; i++) fv.push_back((float)p[i]); return true; };
-    if (!addf("link_pos")) return 0;
-    { size_t cnt = 0; const double *q = m->f64("link_quat", &cnt); if (!q) return 0; for (size_t i = 0; i < cnt / 4; i++) { float mt[9]; quat2mat_h(q + 4 * i, mt); fv.insert(fv.end(), mt, mt + 9); } }
-    if (!addf("link_com") || !addf("link_inertia") || !addf("link_mass") || !addf("dof_axis") || !addf("dof_pos")) return 0;
-    for (size_t r = 0; r < sizeof kKin3Checks / sizeof kKin3Checks[0]; r++) {
-        const Kin3Check &k = kKin3Checks[r];
-        if (k.i && k.ni == (int)iv.size() && k.nf == (int)fv.size() && memcmp(k.i, iv.data(), iv.size() * sizeof(int)) == 0 && memcmp(k.f, fv.data(), fv.size() * sizeof(float)) == 0) return (int)r + 1;
-    }
-    return 0;
+// HSR_NO_CONST=1 never chooses them); any other model runs a generic instance (lanes per env, bound on nv).  A new constant
+// configuration adds its entries here.
+struct PersistInstance {
+    int row;                       // row of kCfgConsts, or -1: a generic instance for ...
+    int group, nv;                 // ... this many lanes per env and (nv >= 0) exactly this many dofs
+    bool tg;                       // pair / geom tables in global memory (LDS budget: 8 workgroups per CU)
+    persist_fn fn, sv;             // the instance and its twin with the solo-server path (persist.h SV), or NULL
+};
+static const PersistInstance kPersistInstances[] = {
+#ifdef HSR_DEV_CFG3
+    // development builds (tools/build_variants.py): only the cfg3 instance is compiled - a sixth of the build time
+    {2, 16, -1, false, k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3>, k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3, true>},
+#else
+    {0, 16, -1, false, k_env_step_mf<16, 2, true, 0, false, DevModel_cfg1>, nullptr},                  // two orthogonal slides
+    {1, 16, -1, false, k_env_step_mf<16, 8, true, 0, false, DevModel_cfg2>, k_env_step_mf<16, 8, true, 0, false, DevModel_cfg2, true>},      // the slides + one block
+    {2, 16, -1, false, k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3>, k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3, true>},    // arm + block
+    {3, 32, -1, false, k_env_step_mf<32, 25, true, 7, false, DevModel_cfg4>, nullptr},                 // arm + three blocks
+    {3, 32, -1, true, k_env_step_mf<32, 25, true, 7, true, DevModel_cfg4>, nullptr},                   // 124 constraint rows per env (compiler.py: eff_njmax)
+    {4, 16, -1, false, k_env_step_mf<16, 13, true, -1, false, DevModel_cupboard>, k_env_step_mf<16, 13, true, -1, false, DevModel_cupboard, true>},   // cupboard with its tables in LDS (HSR_TABLES_GLOBAL=0: 7 workgroups per CU)
+    {4, 16, -1, true, k_env_step_mf<16, 13, true, -1, true, DevModel_cupboard>, k_env_step_mf<16, 13, true, -1, true, DevModel_cupboard, true>},      // 274 candidate pairs
+    {-1, 16, 13, false, k_env_step_mf<16, 13, true>, nullptr},                                          // ndense at run time
+    {-1, 16, -1, false, k_env_step_mf<16, 16, false>, nullptr},
+    {-1, 32, -1, false, k_env_step_mf<32, 32, false>, nullptr},
+#endif
+};
+static const PersistInstance *find_instance(int row, int group, int nv, bool tg) {
+    for (const PersistInstance &p : kPersistInstances)
+        if (p.row == row && p.group == group && (p.nv < 0 || p.nv == nv) && p.tg == tg) return &p;
+    return nullptr;
 }
-static int cfg_const_row(const DevModel &d) {
+static void quat2mat_h(const double *q, float *mt);
+// the row of kCfgConsts whose constant instance may serve the model, -1 if none (or HSR_NO_CONST=1): every scalar field equal, and for a
+// row compiled with its kinematic tree (kin3.h) the tree tables too, value for value (kKin3Checks, in the order tools/gen_cfg_consts.py writes them)
+static int cfg_const_row(const hsr_model *m, const DevModel &d) {
     const char *nc = getenv("HSR_NO_CONST");
     if (nc && strcmp(nc, "0") != 0) return -1;
     int iv[sizeof kCfgConsts[0].i / sizeof(int)]; float fv[sizeof kCfgConsts[0].f / sizeof(float)];
     cfg_const_values(d, iv, fv);
-    for (size_t r = 0; r < sizeof kCfgConsts / sizeof kCfgConsts[0]; r++)
-        if (memcmp(iv, kCfgConsts[r].i, sizeof iv) == 0 && memcmp(fv, kCfgConsts[r].f, sizeof fv) == 0) {
-            // an instance compiled with its kinematic tree (kin3.h) serves only a model whose tree is that one, value for value (hsr_batch_create: kin3_match)
-            if (kKin3Checks[r].i && d.kin3_match != (int)r + 1) return -1;
-            return (int)r;
-        }
-    return -1;
+    int r = 0;
+    const int nrows = (int)(sizeof kCfgConsts / sizeof kCfgConsts[0]);
+    while (r < nrows && !(memcmp(iv, kCfgConsts[r].i, sizeof iv) == 0 && memcmp(fv, kCfgConsts[r].f, sizeof fv) == 0)) r++;
+    if (r == nrows) return -1;
+    const Kin3Check &k = kKin3Checks[r];
+    if (!k.i) return r;
+    std::vector<int> ti = {d.nlink, d.nv};
+    for (const char *n : {"link_parent", "link_free", "link_dofadr", "link_dofnum", "link_qposadr", "dof_type", "dof_qposadr", "dof_link"}) {
+        size_t cnt = 0; const int *p = m->i32(n, &cnt);
+        ti.insert(ti.end(), p, p + cnt);
+    }
+    std::vector<float> tf;
+    auto addf = [&](const char *n) { size_t cnt = 0; const double *p = m->f64(n, &cnt); for (size_t i = 0; i < cnt; i++) tf.push_back((float)p[i]); };
+    addf("link_pos");
+    { size_t cnt = 0; const double *q = m->f64("link_quat", &cnt); for (size_t i = 0; i < cnt / 4; i++) { float mt[9]; quat2mat_h(q + 4 * i, mt); tf.insert(tf.end(), mt, mt + 9); } }
+    for (const char *n : {"link_com", "link_inertia", "link_mass", "dof_axis", "dof_pos"}) addf(n);
+    return k.ni == (int)ti.size() && k.nf == (int)tf.size() && memcmp(k.i, ti.data(), ti.size() * sizeof(int)) == 0
+           && memcmp(k.f, tf.data(), tf.size() * sizeof(float)) == 0 ? r : -1;
 }
 enum { QUEUE_ROUNDS = 64 };
-// the instance with the solo-server path (persist.h SV) of the configurations that have one, else NULL
-static persist_fn persist_kernel_sv(const DevModel &d, int group, bool tg) {
-    const int row = cfg_const_row(d);
-    if (group != 16) return nullptr;
-#ifdef HSR_DEV_CFG3
-    return (!tg && row == 2) ? k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3, true> : nullptr;
-#else
-    if (tg) return row == 4 ? k_env_step_mf<16, 13, true, -1, true, DevModel_cupboard, true> : nullptr;
-    switch (row) {
-    case 1: return k_env_step_mf<16, 8, true, 0, false, DevModel_cfg2, true>;
-    case 2: return k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3, true>;
-    case 4: return k_env_step_mf<16, 13, true, -1, false, DevModel_cupboard, true>;
-    default: return nullptr;
-    }
-#endif
-}
-static persist_fn persist_kernel(const DevModel &d, int group, bool tg = false) {
-    const int row = cfg_const_row(d);
-    const int nv = d.nv;
-#ifdef HSR_DEV_CFG3
-    // development builds (tools/build_variants.py): only the cfg3 instance is compiled - a sixth of the build time
-    return (!tg && row == 2) ? k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3> : nullptr;
-#else
-    if (tg) {      // pair / geom tables in global memory (LDS budget: 8 workgroups per CU)
-        if (row == 4) return k_env_step_mf<16, 13, true, -1, true, DevModel_cupboard>;      // 274 candidate pairs
-        if (row == 3) return k_env_step_mf<32, 25, true, 7, true, DevModel_cfg4>;           // 124 constraint rows per env (compiler.py: eff_njmax)
-        return nullptr;
-    }
-    switch (row) {
-    case 0: return k_env_step_mf<16, 2, true, 0, false, DevModel_cfg1>;            // two orthogonal slides
-    case 1: return k_env_step_mf<16, 8, true, 0, false, DevModel_cfg2>;            // the slides + one block
-    case 2: return k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3>;           // arm + block
-    case 3: return k_env_step_mf<32, 25, true, 7, false, DevModel_cfg4>;           // arm + three blocks
-    case 4: return k_env_step_mf<16, 13, true, -1, false, DevModel_cupboard>;      // cupboard with its tables in LDS (HSR_TABLES_GLOBAL=0: 7 workgroups per CU)
-    default: break;
-    }
-    if (group == 16) {
-        if (nv == 13) return k_env_step_mf<16, 13, true>;                            // ndense at run time
-        return k_env_step_mf<16, 16, false>;
-    }
-    return k_env_step_mf<32, 32, false>;
-#endif
-}
 
 template <typename T>
 static int dalloc(hsr_batch *b, T **p, size_t count) {
@@ -549,6 +531,102 @@ __global__ void k_expand_M(DevState s, float *out, int nv) {   // packed [nM][N]
 
 static inline dim3 grid1(size_t n, int t = 256) { return dim3((unsigned)((n + t - 1) / t)); }
 
+// The persistent kernel: the instance that serves the model (kPersistInstances) and what it needs from the host - the free bodies at the
+// tail of the dof vector, the hulls it stages in LDS, its tables in LDS or in global memory, its dynamic LDS, the workgroups the GPU
+// holds at once.  Decided once, here; every later use reads the record.  A model outside the kernel's lane maps keeps b->kernel == NULL
+// and runs the per-substep chain.
+static int plan_persist(hsr_batch *b, const hsr_model *m) {
+    DevModel &d = b->dm;
+    const int G = b->group;
+    int rc = 0;
+    {   // trailing free bodies: link l owns exactly the dofs [nv - 6 (k + 1), nv - 6 k), lin then ang (the constant instances are matched on nfb too)
+        const int *dn = m->i32("link_dofnum"), *lf = m->i32("link_free"), *da = m->i32("link_dofadr"), *dt = m->i32("dof_type"), *dl = m->i32("dof_link");
+        int nfb = 0;
+        for (int k = 0; 6 * (k + 1) <= d.nv; k++) {
+            const int a0 = d.nv - 6 * (k + 1), l = dl[a0];
+            bool fb = l > 0 && lf[l] && da[l] == a0 && dn[l] == 6;
+            for (int j = 0; fb && j < 6; j++) fb = dl[a0 + j] == l && dt[a0 + j] == (j < 3 ? DOF_FREE_LIN : DOF_FREE_ANG);
+            if (!fb) break;
+            nfb++;
+        }
+        if (nfb * 28 * (64 / G) > 4 * 48) nfb = 0;                  // the per-body accumulators live in the box-box polygon scratch
+        const char *nf = getenv("HSR_NFB");                          // diagnostic: HSR_NFB=0 keeps the per-contact assembly
+        if (nf && atoi(nf) < nfb) nfb = atoi(nf) < 0 ? 0 : atoi(nf);
+        d.nfb = nfb;
+    }
+    int row = cfg_const_row(m, d);
+    if (row >= 0 && kKin3Checks[row].i) {      // kin3.h stages 12 floats per dof and the robot's block of M in the row-scalar region of an env (Kin3Stage): it has to fit
+        const int *lf = m->i32("link_free"), *dl = m->i32("dof_link");
+        int nrd = 0;
+        for (int k = 0; k < d.nv; k++) nrd += lf[dl[k]] ? 0 : 1;
+        const int stage = 12 * d.nv + ((nrd + 3) & ~3) * nrd;
+        const int region = G == 16 ? PersistLayout<16>(d.njmax, b->ds.kstride, d.npair_pad, d.nlink, d.ngeom, d.nstatic_geom).oCnt : PersistLayout<32>(d.njmax, b->ds.kstride, d.npair_pad, d.nlink, d.ngeom, d.nstatic_geom).oCnt;
+        if (stage > region) row = -1;
+    }
+    b->const_row = row;
+    b->kin3 = row >= 0 && kKin3Checks[row].i;
+    {   // hulls staged in LDS by the instances that know their tree at compile time (their kin2 table area is free: persist.h): the hulls of the
+        // deepest links first (the fingers: what the hard envs run MPR on), smaller ones first within a link depth, while they fit
+        const int *gl = m->i32("geom_link"), *gt = m->i32("geom_type"), *ma = m->i32("geom_meshadr"), *mn = m->i32("geom_meshnum"), *lp = m->i32("link_parent");
+        std::vector<int> ldsv(std::max(d.ngeom, 1), -1), src;
+        if (b->kin3) {
+            const int budget = KIN2_FLOATS * d.nlink / 4;
+            auto depth = [&](int l) { int k = 0; while (l > 0) { l = lp[l]; k++; } return k; };
+            std::vector<int> order;
+            for (int g = 0; g < d.ngeom; g++) if (gt[g] == GEOM_MESH && gl[g] > 0 && mn[g] > 0) order.push_back(g);
+            std::stable_sort(order.begin(), order.end(), [&](int a, int bb) { const int da = depth(gl[a]), db = depth(gl[bb]); return da != db ? da > db : mn[a] < mn[bb]; });
+            for (int g : order) if ((int)src.size() + mn[g] <= budget) { ldsv[g] = (int)src.size(); for (int k = 0; k < mn[g]; k++) src.push_back(ma[g] + k); }
+        }
+        int *dl_; if ((rc = dalloc(b, &dl_, ldsv.size()))) return rc;
+        HIPCHK(hipMemcpy(dl_, ldsv.data(), ldsv.size() * sizeof(int), hipMemcpyHostToDevice));
+        d.geom_ldsv = dl_;
+        int *ds_; if ((rc = dalloc(b, &ds_, src.size() + 1))) return rc;
+        if (!src.empty()) HIPCHK(hipMemcpy(ds_, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice));
+        d.ldsv_src = ds_; d.nldsv = (int)src.size();
+    }
+    auto lds_total = [&](bool tg) { return (size_t)sizeof(float) * (G == 16 ? PersistLayout<16>(d.njmax, b->ds.kstride, d.npair_pad, d.nlink, d.ngeom, d.nstatic_geom, tg).total
+                                                                            : PersistLayout<32>(d.njmax, b->ds.kstride, d.npair_pad, d.nlink, d.ngeom, d.nstatic_geom, tg).total); };
+    // a model whose tables cost the eighth workgroup per CU (160 KB / 8 = 20480 B each, static LDS included) reads them from global memory
+    const PersistInstance *in_lds = find_instance(row, G, d.nv, false), *in_global = find_instance(row, G, d.nv, true);
+    const char *tg = getenv("HSR_TABLES_GLOBAL");                    // diagnostic: 0 keeps the tables in LDS
+    hipFuncAttributes fa;
+    b->persist_tg = in_lds && in_global && !(tg && strcmp(tg, "0") == 0)
+                    && hipFuncGetAttributes(&fa, (const void *)in_lds->fn) == hipSuccess && lds_total(false) + fa.sharedSizeBytes > 20480
+                    && hipFuncGetAttributes(&fa, (const void *)in_global->fn) == hipSuccess && lds_total(true) + fa.sharedSizeBytes <= 20480;
+    b->persist_lds_bytes = lds_total(b->persist_tg);
+    const PersistInstance *inst = b->persist_tg ? in_global : in_lds;
+    // what the persistent kernel's lane maps and kinematics assume (kin2.h, persist.h); a model outside it runs the per-substep chain
+    bool ok = d.nq <= G && d.nv <= G && d.nlink <= G && d.nlink <= NLMAX && d.ngeom <= 64 && d.npair < (1 << 14) && d.maxdepth <= 9;
+    {   // the persistent kernel keeps every dof's chain to the root in one 64-bit register, 6 bits per dof (persist.h: anc_c)
+        const int *dp = m->i32("dof_parent");
+        for (int c = 0; ok && c < d.nv; c++) { int depth = 0; for (int k = c; k >= 0 && depth <= 10; k = dp[k]) depth++; if (depth > 10) ok = false; }
+    }
+    {
+        const int *dn = m->i32("link_dofnum"), *lf = m->i32("link_free"), *lp = m->i32("link_parent"), *gl = m->i32("geom_link");
+        for (int l = 1; l < d.nlink; l++) {
+            if (!lf[l] && dn[l] > 3) ok = false;                          // at most three scalar joints per link record
+            if (lf[l] && lp[l] != 0) ok = false;                          // free bodies hang off the world ...
+            if (lf[lp[l]]) ok = false;                                    // ... and carry no children
+        }
+        for (int gi = d.nstatic_geom; gi < d.ngeom; gi++) if (gl[gi] == 0) ok = false;   // static geoms form a prefix of the geom list
+    }
+    if (b->persist_lds_bytes > 160 * 1024) ok = false;
+    if (!inst) ok = false;                                            // development builds carry one instance only
+    if (!ok) { d.nfb = 0; return HSR_OK; }
+    b->kernel = inst->fn;
+    b->kernel_sv = inst->sv;
+    b->persist = true;
+    for (persist_fn f : {b->kernel, b->kernel_sv})
+        if (f && b->persist_lds_bytes > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->persist_lds_bytes));
+    int pb = -1;
+    hipDeviceProp_t prop;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, b->kernel, 64, b->persist_lds_bytes) == hipSuccess && pb > 0
+        && hipGetDeviceProperties(&prop, b->device) == hipSuccess) b->slots = pb * prop.multiProcessorCount;
+    if (getenv("HSR_DEBUG") && hipFuncGetAttributes(&fa, (const void *)b->kernel) == hipSuccess)
+        fprintf(stderr, "[hsrsim] k_env_step_mf<%d>: regs %d, static LDS %zu, dyn LDS %zu, scratch %zu -> %d workgroups per CU\n", G, fa.numRegs, fa.sharedSizeBytes, b->persist_lds_bytes, fa.localSizeBytes, pb);
+    return HSR_OK;
+}
+
 static int batch_init(hsr_batch *b, const hsr_model *m, int n_envs);
 extern "C" int hsr_batch_create(const hsr_model *m, int n_envs, int device_id, hsr_batch **out) {
     if (!m || !out || n_envs <= 0) return fail(HSR_EINVAL, "bad arguments to hsr_batch_create");
@@ -738,107 +816,7 @@ static int batch_init(hsr_batch *b, const hsr_model *m, int n_envs) {
             else HIPCHK(hipFuncSetAttribute((const void *)k_solve_mf<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->mf_lds_bytes));
         }
     }
-    {
-        d.kin3_match = kin3_matching_row(m);
-        if (d.kin3_match) {      // kin3.h stages 12 floats per dof and the robot's block of M in the row-scalar region of an env (Kin3Stage): it has to fit
-            const int *lf = m->i32("link_free"), *dl = m->i32("dof_link");
-            int nrd = 0;
-            for (int k = 0; k < d.nv; k++) nrd += lf[dl[k]] ? 0 : 1;
-            const int stage = 12 * d.nv + ((nrd + 3) & ~3) * nrd;
-            const int region = b->group == 16 ? PersistLayout<16>(d.njmax, b->ds.kstride, d.npair_pad, d.nlink, d.ngeom, d.nstatic_geom).oCnt : PersistLayout<32>(d.njmax, b->ds.kstride, d.npair_pad, d.nlink, d.ngeom, d.nstatic_geom).oCnt;
-            if (stage > region) d.kin3_match = 0;
-        }
-        {   // (before an instance is chosen: the constant instances are matched on nfb too)
-            // trailing free bodies: link l owns exactly the dofs [nv - 6 (k + 1), nv - 6 k), lin then ang
-            const int *dn = m->i32("link_dofnum"), *lf = m->i32("link_free"), *da = m->i32("link_dofadr"), *dt = m->i32("dof_type"), *dl = m->i32("dof_link");
-            int nfb = 0;
-            for (int k = 0; 6 * (k + 1) <= d.nv; k++) {
-                const int a0 = d.nv - 6 * (k + 1), l = dl[a0];
-                bool fb = l > 0 && lf[l] && da[l] == a0 && dn[l] == 6;
-                for (int j = 0; fb && j < 6; j++) fb = dl[a0 + j] == l && dt[a0 + j] == (j < 3 ? DOF_FREE_LIN : DOF_FREE_ANG);
-                if (!fb) break;
-                nfb++;
-            }
-            if (nfb * 28 * (64 / b->group) > 4 * 48) nfb = 0;                  // the per-body accumulators live in the box-box polygon scratch
-            const char *nf = getenv("HSR_NFB");                                // diagnostic: HSR_NFB=0 keeps the per-contact assembly
-            if (nf && atoi(nf) < nfb) nfb = atoi(nf) < 0 ? 0 : atoi(nf);
-            d.nfb = nfb;
-        }
-        {   // hulls staged in LDS by the instances that know their tree at compile time (their kin2 table area is free: persist.h): the hulls of the
-            // deepest links first (the fingers: what the hard envs run MPR on), smaller ones first within a link depth, while they fit
-            const int *gl = m->i32("geom_link"), *gt = m->i32("geom_type"), *ma = m->i32("geom_meshadr"), *mn = m->i32("geom_meshnum"), *lp = m->i32("link_parent");
-            std::vector<int> ldsv(std::max(d.ngeom, 1), -1), src;
-            const char *nh = getenv("HSR_LDS_HULLS");
-            const int crow = cfg_const_row(d);          // (the instance that will run: HSR_NO_CONST=1 and a model that matches no row take a generic one, whose kin2 table occupies the area)
-            if (crow >= 0 && kKin3Checks[crow].i && !(nh && strcmp(nh, "0") == 0)) {
-                const int budget = KIN2_FLOATS * d.nlink / 4;
-                auto depth = [&](int l) { int k = 0; while (l > 0) { l = lp[l]; k++; } return k; };
-                std::vector<int> order;
-                for (int g = 0; g < d.ngeom; g++) if (gt[g] == GEOM_MESH && gl[g] > 0 && mn[g] > 0) order.push_back(g);
-                std::stable_sort(order.begin(), order.end(), [&](int a, int bb) { const int da = depth(gl[a]), db = depth(gl[bb]); return da != db ? da > db : mn[a] < mn[bb]; });
-                for (int g : order) if ((int)src.size() + mn[g] <= budget) { ldsv[g] = (int)src.size(); for (int k = 0; k < mn[g]; k++) src.push_back(ma[g] + k); }
-            }
-            int *dl_; if ((rc = dalloc(b, &dl_, ldsv.size()))) return rc;
-            HIPCHK(hipMemcpy(dl_, ldsv.data(), ldsv.size() * sizeof(int), hipMemcpyHostToDevice));
-            d.geom_ldsv = dl_;
-            int *ds_; if ((rc = dalloc(b, &ds_, src.size() + 1))) return rc;
-            if (!src.empty()) HIPCHK(hipMemcpy(ds_, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice));
-            d.ldsv_src = ds_; d.nldsv = (int)src.size();
-        }
-        auto lds_total = [&](bool tg) { return (size_t)sizeof(float) * (b->group == 16 ? PersistLayout<16>(d.njmax, b->ds.kstride, d.npair_pad, d.nlink, d.ngeom, d.nstatic_geom, tg).total
-                                                                                            : PersistLayout<32>(d.njmax, b->ds.kstride, d.npair_pad, d.nlink, d.ngeom, d.nstatic_geom, tg).total); };
-        b->persist_lds_bytes = lds_total(false);
-        {   // a model whose tables cost the eighth workgroup per CU (160 KB / 8 = 20480 B each, static LDS included) reads them from global memory
-            hipFuncAttributes fa;
-            persist_fn f0 = persist_kernel(d, b->group, false), f1 = persist_kernel(d, b->group, true);
-            if (f1 && hipFuncGetAttributes(&fa, (const void *)f0) == hipSuccess && b->persist_lds_bytes + fa.sharedSizeBytes > 20480
-                && hipFuncGetAttributes(&fa, (const void *)f1) == hipSuccess && lds_total(true) + fa.sharedSizeBytes <= 20480) {
-                b->persist_tg = true;
-                b->persist_lds_bytes = lds_total(true);
-            }
-            const char *tg = getenv("HSR_TABLES_GLOBAL");                    // diagnostic: 0 keeps the tables in LDS
-            if (tg && strcmp(tg, "0") == 0 && b->persist_tg) { b->persist_tg = false; b->persist_lds_bytes = lds_total(false); }
-        }
-        // what the persistent kernel's lane maps and kinematics assume (kin2.h, persist.h); a model outside it runs the per-substep chain
-        bool ok = d.nq <= b->group && d.nv <= b->group && d.nlink <= b->group && d.nlink <= NLMAX && d.ngeom <= 64 && d.npair < (1 << 14) && d.maxdepth <= 9;
-        {   // the persistent kernel keeps every dof's chain to the root in one 64-bit register, 6 bits per dof (persist.h: anc_c)
-            const int *dp = m->i32("dof_parent");
-            for (int c = 0; ok && c < d.nv; c++) { int depth = 0; for (int k = c; k >= 0 && depth <= 10; k = dp[k]) depth++; if (depth > 10) ok = false; }
-        }
-        {
-            const int *dn = m->i32("link_dofnum"), *lf = m->i32("link_free"), *lp = m->i32("link_parent"), *gl = m->i32("geom_link");
-            for (int l = 1; l < d.nlink; l++) {
-                if (!lf[l] && dn[l] > 3) ok = false;                          // at most three scalar joints per link record
-                if (lf[l] && lp[l] != 0) ok = false;                          // free bodies hang off the world ...
-                if (lf[lp[l]]) ok = false;                                    // ... and carry no children
-            }
-            for (int gi = d.nstatic_geom; gi < d.ngeom; gi++) if (gl[gi] == 0) ok = false;   // static geoms form a prefix of the geom list
-        }
-        if (b->persist_lds_bytes > 160 * 1024) ok = false;
-        if (!persist_kernel(d, b->group, b->persist_tg)) ok = false;      // development builds carry one instance only
-        b->persist_ok = ok;
-        if (!ok) d.nfb = 0;
-        const char *pe = getenv("HSR_PERSIST");
-        b->persist = ok && !(pe && strcmp(pe, "0") == 0);
-        if (ok && b->persist_lds_bytes > 48 * 1024)
-            HIPCHK(hipFuncSetAttribute((const void *)persist_kernel(d, b->group, b->persist_tg), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->persist_lds_bytes));
-    }
-    b->solo_ok = b->persist_ok && persist_kernel_sv(d, b->group, b->persist_tg) != nullptr;          // an instance with the server path exists
-    if (b->solo_ok && b->persist_lds_bytes > 48 * 1024)
-        HIPCHK(hipFuncSetAttribute((const void *)persist_kernel_sv(d, b->group, b->persist_tg), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->persist_lds_bytes));
-    if (b->persist_ok) {
-        int pb = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, persist_kernel(d, b->group, b->persist_tg), 64, b->persist_lds_bytes) == hipSuccess && pb > 0
-            && hipGetDeviceProperties(&prop, b->device) == hipSuccess) b->slots = pb * prop.multiProcessorCount;
-    }
-    if (getenv("HSR_DEBUG") && b->persist_ok) {
-        int pb = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&pb, persist_kernel(d, b->group, b->persist_tg), 64, b->persist_lds_bytes);
-        hipFuncAttributes fb;
-        if (hipFuncGetAttributes(&fb, (const void *)persist_kernel(d, b->group, b->persist_tg)) == hipSuccess)
-            fprintf(stderr, "[hsrsim] k_env_step_mf<%d>: regs %d, static LDS %zu, dyn LDS %zu, scratch %zu -> %d workgroups per CU\n", b->group, fb.numRegs, fb.sharedSizeBytes, b->persist_lds_bytes, fb.localSizeBytes, pb);
-    }
+    if ((rc = plan_persist(b, m))) return rc;
     {
         const size_t kb = (size_t)64 * (b->ds.kstride + 24 * d.nlink + 1) * sizeof(float);
         if (kb > 160 * 1024) return fail(HSR_EINVAL, "kinematics tile exceeds LDS");
@@ -910,7 +888,7 @@ static void clear_margins(hsr_batch *b) {
 }
 extern "C" int hsr_batch_set_persistent(hsr_batch *b, int on) {
     NULLCHK(b);
-    const bool want = on != 0 && b->persist_ok;
+    const bool want = on != 0 && b->kernel;
     if (want && !b->persist) { hipSetDevice(b->device); clear_margins(b); }      // the per-substep chain does not maintain the margins
     b->persist = want;
     return b->persist ? 1 : 0;
@@ -918,8 +896,7 @@ extern "C" int hsr_batch_set_persistent(hsr_batch *b, int on) {
 extern "C" int hsr_batch_is_persistent(const hsr_batch *b) {
     NULLCHK(b);
     if (!b->persist) return 0;
-    const int row = cfg_const_row(b->dm);
-    return 1 | (row >= 0 ? 2 : 0) | ((row >= 0 && kKin3Checks[row].i) ? 4 : 0);
+    return 1 | (b->const_row >= 0 ? 2 : 0) | (b->kin3 ? 4 : 0);
 }
 extern "C" int hsr_batch_set_debug(hsr_batch *b, int on) { if (!b) return fail(HSR_EINVAL, "null batch"); b->debug_store = (on & 1) != 0; b->test_hooks = on & (6 | 16 | 32 | 64 | 128); return HSR_OK; }
 extern "C" int hsr_batch_set_schedule(hsr_batch *b, int on) { NULLCHK(b); b->schedule = on != 0; return HSR_OK; }
@@ -935,7 +912,7 @@ extern "C" int hsr_batch_set_solo(hsr_batch *b, int servers, float trips) {
     if (servers < 0 || trips < 0.f) return fail(HSR_EINVAL, "hsr_batch_set_solo: servers >= 0, trips >= 0");
     b->solo_servers = servers;
     if (trips > 0.f) b->solo_trips = trips;
-    return b->solo_ok ? HSR_OK : 1;          // 1: accepted, but this model's kernel instance has no server path (the setting has no effect)
+    return b->kernel_sv ? HSR_OK : 1;          // 1: accepted, but this model's kernel instance has no server path (the setting has no effect)
 }
 extern "C" int hsr_batch_solo_handovers(hsr_batch *b, int *out) {
     if (!b || !out) return fail(HSR_EINVAL, "null argument");
@@ -1234,7 +1211,7 @@ extern "C" int hsr_batch_step_dev(hsr_batch *b, const float *d_ctrl, int n_subst
         // solo servers need the queue (a hard env leaves its task at the end of a round) and the env -> slot table
         // (a hand-over ticket packs env | substep << 20 into one int that must stay non-negative: fewer than 2048 substeps, at most 2^20 envs - beyond
         // that the launch simply runs without servers)
-        const bool solo = b->solo_ok && b->solo_servers > 0 && b->solo_servers <= 4096 && sched && b->slots > 0 && n_substeps >= 3 * chunk && n_substeps < 2048 && b->N <= (1 << 20)
+        const bool solo = b->kernel_sv && b->solo_servers > 0 && b->solo_servers <= 4096 && sched && b->slots > 0 && n_substeps >= 3 * chunk && n_substeps < 2048 && b->N <= (1 << 20)
                           && (T + b->solo_servers <= b->slots || 4 * b->solo_servers <= b->slots);
         const bool qon = b->slots > 0 && n_substeps >= 2 * chunk && (solo || b->queue == 1 || (b->queue < 0 && T > b->slots));
         int grid = T;
@@ -1248,7 +1225,7 @@ extern "C" int hsr_batch_step_dev(hsr_batch *b, const float *d_ctrl, int n_subst
         }
         hipEvent_t k0 = nullptr, k1 = nullptr;
         if (b->kernel_log) { hipEventCreate(&k0); hipEventCreate(&k1); hipEventRecord(k0, st); }
-        hipLaunchKernelGGL(dsl.solo_servers > 0 ? persist_kernel_sv(b->dm, b->group, b->persist_tg) : persist_kernel(b->dm, b->group, b->persist_tg), dim3(grid), dim3(64), b->persist_lds_bytes, st, (const DevModel *)b->d_dm, dsl, n_substeps, goal_body, geofence, (b->debug_store ? 1 : 0) | (b->test_hooks & ~32) | (b->mpr_warm ? 0 : 8), io);
+        hipLaunchKernelGGL(dsl.solo_servers > 0 ? b->kernel_sv : b->kernel, dim3(grid), dim3(64), b->persist_lds_bytes, st, (const DevModel *)b->d_dm, dsl, n_substeps, goal_body, geofence, (b->debug_store ? 1 : 0) | (b->test_hooks & ~32) | (b->mpr_warm ? 0 : 8), io);
         if ((b->test_hooks & 32) && b->ds.q_err) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)b->ds.q_err, 1, 1, st));      // tests: what q_claim's watchdog does when a ticket is never served
         if (b->kernel_log) { hipEventRecord(k1, st); b->klog.push_back({k0, k1}); }
         if (b->profiling) { hipEvent_t ev; hipEventCreate(&ev); hipEventRecord(ev, st); b->kev.push_back(ev); }   // slots 0,1 empty; slot 2 = the persistent kernel

@@ -39,7 +39,6 @@ struct DevModel {
     const int *geom_ldsv;             // [ngeom] hulls staged in LDS by the persistent kernel (persist.h: hull area): first float4 slot, or -1 (the hull stays in global memory)
     const int *ldsv_src;              // [nldsv] vertex index in mesh_vert4 of every staged slot
     int nldsv;
-    int kin3_match;                   // host side: row + 1 of the constant instance (cfg_consts.h) whose compile-time tree tables equal this model's, 0 = none
 };
 
 // env-step inputs / outputs of the caller (hsr_batch_step_dev), env-major as the C-ABI hands them over: the persistent kernel reads ctrl

@@ -296,6 +296,10 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
         typedef typename Kin3Of<MT>::type KD;
         constexpr bool KIN3 = KD::ok && EXACT;
         if constexpr (KIN3) {
+            // kin3_run: lane = link in its link-parallel parts, and the 16-float records of all links go where the moving geoms' placements go afterwards
+            static_assert(KD::NL <= G, "kin3_run: one lane per link");
+            static_assert(16 * KD::NL <= (16 * (MT::ngeom - MT::nstatic_geom) > 8 * G ? 16 * (MT::ngeom - MT::nstatic_geom) : 8 * G),
+                          "kin3_run: the link records fit the moving-geom placement area (PersistLayout: kin_tmp)");
 #ifndef HSR_K3_NORUN
             kin3_run<KD, G, NK>(c, m.gravz, qposL, qvelL, poseL, recL, kAng, qvelL + G, m.link_com, m.link_inertia, m.link_mass);          // (link records where the geom placements go afterwards)
 #endif

@@ -711,6 +711,28 @@ def test_constant_instances_equal_the_generic_ones(models, cfg, monkeypatch):
     assert np.percentile(d, 99) < 1e-4 and np.median(d) < 1e-6
 
 
+# the persistent-kernel instance of every test model with the constant instances allowed (HSR_NO_CONST=0): kernel_flags() and whether the
+# instance has the solo-server path.  nq18 does not fit the lane maps (the per-substep chain); the other test models run a generic instance
+KERNEL_INSTANCES = {"cfg1": (7, False), "cfg2": (7, True), "cfg3": (7, True), "cfg4": (7, False), "cupboard": (7, True), "cfg3_setxml": (7, True),
+                    "nq18": (0, False), "nv11": (1, False), "nv23": (1, False), "static1": (1, False), "meshrest4": (1, False), "meshrest1": (1, False)}
+
+
+@pytest.mark.parametrize("no_const", ["0", "1"])
+@pytest.mark.parametrize("cfg", list(KERNEL_INSTANCES))
+def test_kernel_instance_chosen_at_creation(models, cfg, no_const, monkeypatch):
+    """The whole decision table of hsr_batch_create: which persistent-kernel instance serves a model (kernel_flags: constant scalars,
+    compile-time tree) and whether it carries the solo-server path (set_solo is True exactly then).  HSR_NO_CONST=1 leaves the generic
+    instances, none of which has servers."""
+    flags, solo = KERNEL_INSTANCES[cfg]
+    if no_const == "1":
+        flags, solo = flags & 1, False
+    monkeypatch.setenv("HSR_NO_CONST", no_const)
+    sim = hs.BatchSim(models[cfg], 8)
+    assert sim.kernel_flags() == flags, sim.kernel_flags()
+    assert sim.set_solo(1, 1.0) == solo
+    sim.close()
+
+
 @pytest.mark.parametrize("cfg", ["cfg3", "cfg4"])
 def test_work_queue_never_changes_a_result(models, cfg):
     """The work queue of the persistent kernel (rounds of a few substeps, workgroups taking (task, round) tickets; automatic when a batch
