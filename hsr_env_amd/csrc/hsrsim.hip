@@ -22,6 +22,7 @@
 #include "solve_g.h"
 #include "solve_mf.h"
 #include "persist.h"
+#include "render.h"
 #include "cfg_consts.h"
 
 static thread_local char g_err[512] = "";
@@ -47,6 +48,11 @@ struct hsr_model {
     std::vector<std::pair<int, int>> joint_qposadr;
     // host copies used to build device tables for each batch's device
     std::vector<float> ctrlrange, qpos0;
+    std::vector<std::string> geom_names;
+    // face planes of the mesh hulls (hull_planes_build, on first use): float4 (n, w) with n.x <= w inside, per geom offset / count
+    mutable std::vector<float> hull_planes;
+    mutable std::vector<int> hull_off, hull_cnt;
+    mutable bool hull_done = false;
 
     const double *f64(const char *n, size_t *count = nullptr) const {
         auto it = entries.find(n);
@@ -178,6 +184,8 @@ extern "C" int hsr_model_load(const void *blob, size_t len, hsr_model **out) {
         size_t bp = json_find_key(m->json, "body", np), jp = json_find_key(m->json, "joint", np);
         if (bp != std::string::npos) m->body_names = json_string_list(m->json, bp);
         if (jp != std::string::npos) m->joint_names = json_string_list(m->json, jp);
+        size_t gp = json_find_key(m->json, "geom", np);
+        if (gp != std::string::npos) m->geom_names = json_string_list(m->json, gp);
     }
     size_t qp = json_find_key(m->json, "joint_qposadr");
     if (qp != std::string::npos) m->joint_qposadr = json_pair_list(m->json, qp);
@@ -213,6 +221,60 @@ extern "C" int hsr_model_joint_qpos_addr(const hsr_model *m, const char *name, i
     for (size_t i = 0; i < m->joint_names.size() && i < m->joint_qposadr.size(); i++)
         if (m->joint_names[i] == name) { *start = m->joint_qposadr[i].first; *end = m->joint_qposadr[i].first + m->joint_qposadr[i].second; return HSR_OK; }
     return fail(HSR_ENAME, "unknown joint '%s'", name);
+}
+
+// Face planes of the mesh hulls (the blob stores the hull vertices only; the ray caster clips rays against the faces).  Brute force
+// in double over vertex triples: the plane through three vertices is a face when no vertex lies outside it by more than 1e-9 of
+// the hull's size (the scan stops at the first vertex on either side that disagrees); coplanar triples of one facet give the same
+// plane and are merged.  At most 256 vertices per hull: ~2.7 M triples, most rejected after a few vertices.
+static void hull_planes_build(const hsr_model *m) {
+    if (m->hull_done) return;
+    const int ng = m->sizes[HSR_NGEOM];
+    const int *gt = m->i32("geom_type"), *ma = m->i32("geom_meshadr"), *mn = m->i32("geom_meshnum");
+    const double *mv = m->f64("mesh_vert");
+    m->hull_off.assign(ng, 0); m->hull_cnt.assign(ng, 0); m->hull_planes.clear();
+    for (int g = 0; g < ng; g++) {
+        m->hull_off[g] = (int)(m->hull_planes.size() / 4);
+        if (gt[g] != GEOM_MESH) continue;
+        const int nv = mn[g];
+        const double *V = mv + 3 * (size_t)ma[g];
+        double size = 0;
+        for (int i = 0; i < 3 * nv; i++) size = std::max(size, fabs(V[i]));
+        const double tol = 1e-9 * size;
+        std::vector<double> pl;                            // accepted planes: nx ny nz w
+        for (int i = 0; i < nv; i++) for (int j = i + 1; j < nv; j++) for (int k = j + 1; k < nv; k++) {
+            const double *a = V + 3 * i, *b = V + 3 * j, *c = V + 3 * k;
+            const double u[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, w[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+            double n[3] = {u[1] * w[2] - u[2] * w[1], u[2] * w[0] - u[0] * w[2], u[0] * w[1] - u[1] * w[0]};
+            const double len = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+            if (len <= 1e-12 * size * size) continue;      // (nearly) collinear
+            for (double &x : n) x /= len;
+            const double d = n[0] * a[0] + n[1] * a[1] + n[2] * a[2];
+            bool above = false, below = false;
+            for (int q = 0; q < nv && !(above && below); q++) {
+                const double sd = n[0] * V[3 * q] + n[1] * V[3 * q + 1] + n[2] * V[3 * q + 2] - d;
+                above |= sd > tol; below |= sd < -tol;
+            }
+            if (above && below) continue;
+            const double sg = above ? -1.0 : 1.0;          // orient outward: every vertex at n.x <= w
+            const double cand[4] = {sg * n[0], sg * n[1], sg * n[2], sg * d};
+            bool dup = false;
+            for (size_t p = 0; p < pl.size() && !dup; p += 4)
+                dup = fabs(pl[p] - cand[0]) + fabs(pl[p + 1] - cand[1]) + fabs(pl[p + 2] - cand[2]) < 1e-7 && fabs(pl[p + 3] - cand[3]) <= 100 * tol;
+            if (!dup) pl.insert(pl.end(), cand, cand + 4);
+        }
+        for (double x : pl) m->hull_planes.push_back((float)x);
+        m->hull_cnt[g] = (int)(pl.size() / 4);
+    }
+    m->hull_done = true;
+}
+extern "C" int hsr_model_hull_planes(const hsr_model *m, int geom, float *out, int cap) {
+    if (!m || geom < 0 || geom >= m->sizes[HSR_NGEOM]) return fail(HSR_EINVAL, "hull_planes: bad geom");
+    if (m->i32("geom_type")[geom] != GEOM_MESH) return fail(HSR_EINVAL, "hull_planes: geom is not a mesh");
+    hull_planes_build(m);
+    const int n = m->hull_cnt[geom];
+    if (out) for (int i = 0; i < std::min(n, cap); i++) for (int k = 0; k < 4; k++) out[4 * i + k] = m->hull_planes[4 * (size_t)(m->hull_off[geom] + i) + k];
+    return n;
 }
 
 // ------------------------------------------------------------------ batch
@@ -262,6 +324,13 @@ struct hsr_batch {
     float solo_trips = 3.5f;       // hand-over threshold: Newton iterations per substep over a round
     bool kernel_log = false;       // hsr_batch_set_profiling(b, 2): an event pair around every launch of the persistent kernel, no synchronisation
     std::vector<std::pair<hipEvent_t, hipEvent_t>> klog;
+    // ray caster (hsr_batch_render*): its own tables and buffers, built on first use; it never touches the simulation state
+    float4 *d_planes = nullptr;    // hull face planes of every mesh geom
+    int2 *d_prange = nullptr;      // [ngeom] (offset, count) into d_planes
+    float4 *d_rgba = nullptr;      // [ngeom] colours of the next render
+    std::vector<float> rgba_host;  // what d_rgba holds
+    void *d_rimg = nullptr;        // staging of the host variant: rgb | depth | segid
+    size_t rimg_bytes = 0;
 };
 
 // global copies of the two constant LDS tables of the persistent kernel (same packing: kin2.h)
@@ -845,6 +914,7 @@ extern "C" void hsr_batch_destroy(hsr_batch *b) {
     if (b->stream) hipStreamSynchronize(b->stream);
     for (auto &kv : b->graphs) hipGraphExecDestroy(kv.second);
     for (void *p : b->allocs) hipFree(p);
+    if (b->d_rimg) hipFree(b->d_rimg);
     for (hipEvent_t ev : b->kev) hipEventDestroy(ev);
     for (auto &pr : b->klog) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     if (b->ev0) hipEventDestroy(b->ev0);
@@ -1384,5 +1454,120 @@ extern "C" int hsr_batch_block_times(hsr_batch *b, unsigned long long *out, int 
 extern "C" int hsr_batch_last_timing(hsr_batch *b, float *total_ms, float *kernel_ms, int *launches) { NULLCHK(b);
     if (total_ms) *total_ms = b->last_total_ms;
     for (int k = 0; k < 3; k++) { if (kernel_ms) kernel_ms[k] = b->last_kernel_ms[k]; if (launches) launches[k] = b->last_launches[k]; }
+    return HSR_OK;
+}
+
+// ------------------------------------------------------------------ rendering (render.h)
+// The default palette (hsr_env_amd/render.py: default_palette restates it): planes .4 .3 .2 (world.xml floor class), the cupboard's
+// `block` .8 .1 .1, injected blocks `block<i>` the i-th colour of the reference's injection list (hsr/util.py), the robot's geoms
+// (from its first to its last geom named `link:mesh`) .33 .33 .33 (hsr.mjcf), every other geom .7 .7 .7 (world.xml box class).
+static void default_palette(const hsr_model *m, std::vector<float> &out) {
+    static const float blocks[7][3] = {{0, 1, 0}, {0, 0, 1}, {0, 1, 1}, {1, 0, 0}, {1, 0, 1}, {1, 1, 0}, {1, 1, 1}};
+    const int ng = m->sizes[HSR_NGEOM];
+    const int *gt = m->i32("geom_type");
+    auto block_index = [&](int g) -> int {                 // -2: not a block, -1: the cupboard's `block`, else i of `block<i>[:...]`
+        if (g >= (int)m->geom_names.size()) return -2;
+        const std::string &nm = m->geom_names[g];
+        if (nm.compare(0, 5, "block") != 0) return -2;
+        size_t i = 5;
+        while (i < nm.size() && isdigit((unsigned char)nm[i])) i++;
+        if (i < nm.size() && nm[i] != ':') return -2;
+        return i == 5 ? (i == nm.size() ? -1 : -2) : atoi(nm.c_str() + 5);
+    };
+    int first = ng, last = -1;
+    for (int g = 0; g < ng && g < (int)m->geom_names.size(); g++)
+        if (block_index(g) == -2 && m->geom_names[g].find(':') != std::string::npos) { first = std::min(first, g); last = g; }
+    out.assign(4 * (size_t)ng, 1.f);
+    for (int g = 0; g < ng; g++) {
+        float *c = out.data() + 4 * g;
+        const int bi = block_index(g);
+        if (gt[g] == GEOM_PLANE) { c[0] = .4f; c[1] = .3f; c[2] = .2f; }
+        else if (bi == -1) { c[0] = .8f; c[1] = .1f; c[2] = .1f; }
+        else if (bi >= 0) { for (int k = 0; k < 3; k++) c[k] = blocks[bi % 7][k]; }
+        else if (g >= first && g <= last) { c[0] = c[1] = c[2] = .33f; }
+        else { c[0] = c[1] = c[2] = .7f; }
+    }
+}
+
+static int render_launch(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
+                         uint8_t *d_rgb, float *d_depth, int32_t *d_segid) {
+    NULLCHK(b);
+    if (!cam) return fail(HSR_EINVAL, "render: null camera");
+    if (width < 1 || width > 4096 || height < 1 || height > 4096) return fail(HSR_EINVAL, "render: width and height must be in 1..4096");
+    for (int k = 0; k < 9; k++) if (!std::isfinite(cam[k])) return fail(HSR_EINVAL, "render: non-finite camera");
+    if (!(cam[6] > 0.f && cam[6] < 180.f)) return fail(HSR_EINVAL, "render: fovy must lie in (0, 180) degrees");
+    if (!(cam[7] > 0.f) || !(cam[8] > cam[7])) return fail(HSR_EINVAL, "render: need 0 < znear < zfar");
+    const hsr_model *m = b->model;
+    const DevModel &d = b->dm;
+    if (track_body >= d.nbody || (track_body >= 0 && m->i32("body_mocap")[track_body])) return fail(HSR_EINVAL, "render: bad track_body");
+    HIPCHK(hipSetDevice(b->device));
+    if (!b->d_planes) {
+        hull_planes_build(m);
+        std::vector<int2> pr(std::max(d.ngeom, 1));
+        for (int g = 0; g < d.ngeom; g++) { pr[g].x = m->hull_off[g]; pr[g].y = m->hull_cnt[g]; }
+        int rc;
+        if ((rc = dalloc(b, &b->d_prange, pr.size()))) return rc;
+        HIPCHK(hipMemcpy(b->d_prange, pr.data(), pr.size() * sizeof(int2), hipMemcpyHostToDevice));
+        if ((rc = dalloc(b, &b->d_rgba, (size_t)std::max(d.ngeom, 1)))) return rc;
+        float4 *dp;
+        if ((rc = dalloc(b, &dp, std::max<size_t>(m->hull_planes.size() / 4, 1)))) return rc;
+        HIPCHK(hipMemcpy(dp, m->hull_planes.data(), m->hull_planes.size() * sizeof(float), hipMemcpyHostToDevice));
+        b->d_planes = dp;
+    }
+    std::vector<float> pal;
+    if (geom_rgba) pal.assign(geom_rgba, geom_rgba + 4 * (size_t)d.ngeom);
+    else default_palette(m, pal);
+    if (pal != b->rgba_host) {             // a new palette: wait for renders still reading the old one
+        HIPCHK(hipStreamSynchronize(b->stream));
+        HIPCHK(hipMemcpy(b->d_rgba, pal.data(), pal.size() * sizeof(float), hipMemcpyHostToDevice));
+        b->rgba_host.swap(pal);
+    }
+    RenderCam c{};
+    const double az = cam[4] * M_PI / 180.0, el = cam[5] * M_PI / 180.0, ty = tan(cam[6] * M_PI / 360.0);
+    const double f[3] = {cos(el) * cos(az), cos(el) * sin(az), sin(el)}, u[3] = {-sin(el) * cos(az), -sin(el) * sin(az), cos(el)};
+    const double r[3] = {f[1] * u[2] - f[2] * u[1], f[2] * u[0] - f[0] * u[2], f[0] * u[1] - f[1] * u[0]};
+    for (int k = 0; k < 3; k++) { c.fwd[k] = (float)f[k]; c.up[k] = (float)u[k]; c.right[k] = (float)r[k]; c.lookat[k] = cam[k]; }
+    c.dist = cam[3]; c.tany = (float)ty; c.tanx = (float)(ty * width / height); c.znear = cam[7]; c.zfar = cam[8];
+    c.track_link = -1;
+    if (track_body >= 0) {
+        c.track_link = m->i32("body_link")[track_body];
+        for (int k = 0; k < 3; k++) c.track_off[k] = (float)m->f64("body_pos")[3 * track_body + k];
+    }
+    c.W = width; c.H = height; c.tiles_x = (width + 15) / 16; c.ntiles = c.tiles_x * ((height + 15) / 16);
+    const size_t lds = ((size_t)RREC * d.ngeom + 4) * sizeof(float);
+    const int per_launch = std::max(1, (1 << 30) / c.ntiles);          // grid.x stays below 2^31
+    for (int e0 = 0; e0 < b->N; e0 += per_launch) {
+        c.env0 = e0;
+        const int ne = std::min(per_launch, b->N - e0);
+        hipLaunchKernelGGL(k_render, dim3((unsigned)(ne * c.ntiles)), dim3(256), lds, b->stream, b->dm, b->ds, c, (const float4 *)b->d_planes,
+                           (const int2 *)b->d_prange, (const float4 *)b->d_rgba, d_rgb, d_depth, d_segid);
+    }
+    HIPCHK(hipGetLastError());
+    return HSR_OK;
+}
+extern "C" int hsr_batch_render_dev(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
+                                    uint8_t *d_rgb, float *d_depth, int32_t *d_segid) {
+    return render_launch(b, cam, track_body, width, height, geom_rgba, d_rgb, d_depth, d_segid);
+}
+extern "C" int hsr_batch_render(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
+                                uint8_t *rgb, float *depth, int32_t *segid) {
+    NULLCHK(b);
+    const size_t npx = (size_t)b->N * (size_t)std::max(width, 0) * (size_t)std::max(height, 0);
+    const size_t o_depth = (3 * npx + 15) & ~(size_t)15, o_seg = o_depth + 4 * npx, bytes = o_seg + 4 * npx;
+    if (width >= 1 && width <= 4096 && height >= 1 && height <= 4096 && bytes > b->rimg_bytes) {
+        HIPCHK(hipSetDevice(b->device));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (b->d_rimg) { HIPCHK(hipFree(b->d_rimg)); b->d_rimg = nullptr; b->rimg_bytes = 0; }
+        HIPCHK(hipMalloc(&b->d_rimg, bytes));
+        b->rimg_bytes = bytes;
+    }
+    uint8_t *base = (uint8_t *)b->d_rimg;
+    int rc = render_launch(b, cam, track_body, width, height, geom_rgba, rgb ? base : nullptr, depth ? (float *)(base + o_depth) : nullptr,
+                           segid ? (int32_t *)(base + o_seg) : nullptr);
+    if (rc) return rc;
+    if (rgb) HIPCHK(hipMemcpyAsync(rgb, base, 3 * npx, hipMemcpyDeviceToHost, b->stream));
+    if (depth) HIPCHK(hipMemcpyAsync(depth, base + o_depth, 4 * npx, hipMemcpyDeviceToHost, b->stream));
+    if (segid) HIPCHK(hipMemcpyAsync(segid, base + o_seg, 4 * npx, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
     return HSR_OK;
 }

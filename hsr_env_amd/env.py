@@ -249,8 +249,17 @@ class VecHSREnv:
     def get_body_com(self, body_name):
         return self._squeeze(self.sim.body_xpos(self.model.body_id(body_name)))
 
-    def render(self, *a, **k):
-        raise NotImplementedError("camera-free observations only (SURVEY.md section 2, #2)")
+    def render(self, mode="rgb_array", width=500, height=500, camera=None):
+        """hsr/mujoco_env.py:105-125 for every env: 'rgb_array' -> uint8 [N,H,W,3], 'depth_array' -> float32 [N,H,W] (distance along
+        the camera axis), row 0 at the top; one env's image alone when n_envs == 1.  camera: render.Camera (None: the model's
+        default_camera).  A ray caster over the collision geoms (hsr_env_amd/render.py).  'human' needs a display: NotImplementedError."""
+        if mode == "rgb_array":
+            return self._squeeze(self.sim.render(width, height, camera, rgb=True))
+        if mode == "depth_array":
+            return self._squeeze(self.sim.render(width, height, camera, rgb=False, depth=True))
+        if mode == "human":
+            raise NotImplementedError("render('human') needs a display; use 'rgb_array' (python -m hsr_env_amd.render writes images)")
+        raise ValueError(f"unknown render mode {mode!r}")
 
     def close(self):
         if getattr(self.sim, "close", None):

@@ -1,0 +1,149 @@
+"""Batched rendering of the envs (include/hsrsim.h: hsr_batch_render): the camera, the default palette and a command that writes
+one PPM image per env.
+
+The images come from a ray caster over the COLLISION geoms, the only geoms the model blob carries (compiler.py drops the visual-only
+meshes): the robot appears as its convex collision hulls.  Shading is fixed and simple (DESIGN.md section f): MuJoCo's default
+headlight (ambient .1, diffuse .4) plus the scene's overhead light taken as directional from +z (diffuse .5); no shadows, specular,
+textures or transparency, so the pixels are not MuJoCo's.
+
+    python -m hsr_env_amd.render --config cfg3 --envs 4 --size 256 --out DIR [--track block0]
+"""
+from __future__ import annotations
+
+import argparse
+from dataclasses import dataclass
+from pathlib import Path
+
+import numpy as np
+
+from .compiler import Model, link_kinematics, load_config, quat_to_mat
+
+DEFAULT_SIZE = 500                        # hsr/mujoco_env.py:17
+
+GEOM_PLANE = 0
+
+
+@dataclass
+class Camera:
+    """MuJoCo free camera: the camera looks at `lookat` from `distance` away, `azimuth` / `elevation` in degrees (elevation < 0
+    looks down), vertical field of view `fovy` in degrees, clip distances `znear` / `zfar` along the camera axis.  With
+    `track_body` set (a body id) every env looks at that body's origin plus `lookat`."""
+    lookat: tuple = (0.0, 0.0, 0.0)
+    distance: float = 2.0
+    azimuth: float = 90.0
+    elevation: float = -45.0
+    fovy: float = 45.0
+    znear: float = 0.01
+    zfar: float = 50.0
+    track_body: int = -1
+
+    def as_array(self) -> np.ndarray:
+        """The cam[9] of hsr_batch_render: lookat3 distance azimuth elevation fovy znear zfar."""
+        return np.array([*self.lookat, self.distance, self.azimuth, self.elevation, self.fovy, self.znear, self.zfar], np.float32)
+
+
+def scene_bounds(model: Model):
+    """Centre and extent of the scene: the centre and half-diagonal of the axis-aligned box around the bounding spheres of the
+    non-plane geoms at qpos0 (this project's definition; MuJoCo's stat.center / stat.extent are computed differently)."""
+    xpos, xquat = link_kinematics(model, model.qpos0)
+    lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
+    for g in range(model.ngeom):
+        if model.geom_type[g] == GEOM_PLANE:
+            continue
+        l = model.geom_link[g]
+        c = xpos[l] + quat_to_mat(xquat[l]) @ model.geom_pos[g]
+        r = model.geom_rbound[g]
+        lo, hi = np.minimum(lo, c - r), np.maximum(hi, c + r)
+    return (lo + hi) / 2, float(np.linalg.norm(hi - lo) / 2)
+
+
+def default_camera(model: Model, track_body: int = -1) -> Camera:
+    """In the manner of MuJoCo's default free camera: azimuth 90, elevation -45, distance 1.5 extent, fovy 45, znear 0.01 extent,
+    zfar 50 extent, looking at the scene centre (scene_bounds).  Close to mujoco-py's default viewpoint, not equal to it: centre and
+    extent are this project's.  With track_body >= 0 the camera looks at that body's origin instead."""
+    centre, extent = scene_bounds(model)
+    lookat = (0.0, 0.0, 0.0) if track_body >= 0 else tuple(float(x) for x in centre)
+    return Camera(lookat=lookat, distance=1.5 * extent, azimuth=90.0, elevation=-45.0, fovy=45.0,
+                  znear=0.01 * extent, zfar=50.0 * extent, track_body=int(track_body))
+
+
+# colours of the reference's block injection (hsr/util.py: rgba list of mutate_xml), block0 first
+_BLOCK_RGB = [(0, 1, 0), (0, 0, 1), (0, 1, 1), (1, 0, 0), (1, 0, 1), (1, 1, 0), (1, 1, 1)]
+
+
+def _block_index(name: str):
+    """None: not a block; -1: the cupboard scene's `block`; i: `block<i>` (optionally `block<i>:mesh`)."""
+    if not name.startswith("block"):
+        return None
+    stem = name[5:].split(":")[0]
+    if stem == "":
+        return -1 if name == "block" else None
+    return int(stem) if stem.isdigit() else None
+
+
+def default_palette(model: Model) -> np.ndarray:
+    """[ngeom, 4] float32 colours from the scene's MJCF classes (the library's palette when geom_rgba is NULL): planes .4 .3 .2
+    (world.xml floor class), robot geoms .33 .33 .33 (hsr.mjcf; the geoms from the first to the last one named `link:mesh`),
+    injected blocks `block<i>` the i-th colour of the reference's injection (block0 green), the cupboard's `block` .8 .1 .1,
+    every other static geom .7 .7 .7 (world.xml box class).  Alpha is 1 and ignored."""
+    names = model.names["geom"]
+    robot = [g for g, nm in enumerate(names) if _block_index(nm) is None and ":" in nm]
+    first, last = (min(robot), max(robot)) if robot else (model.ngeom, -1)
+    out = np.ones((model.ngeom, 4), np.float32)
+    for g in range(model.ngeom):
+        bi = _block_index(names[g]) if g < len(names) else None
+        if model.geom_type[g] == GEOM_PLANE:
+            rgb = (.4, .3, .2)
+        elif bi == -1:
+            rgb = (.8, .1, .1)
+        elif bi is not None:
+            rgb = _BLOCK_RGB[bi % 7]
+        elif first <= g <= last:
+            rgb = (.33, .33, .33)
+        else:
+            rgb = (.7, .7, .7)
+        out[g, :3] = rgb
+    return out
+
+
+def write_ppm(path, rgb: np.ndarray):
+    """Binary PPM (P6) of an [H, W, 3] uint8 image."""
+    h, w, _ = rgb.shape
+    Path(path).write_bytes(b"P6\n%d %d\n255\n" % (w, h) + np.ascontiguousarray(rgb, np.uint8).tobytes())
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="render every env of a batch to PPM images after a few random actions")
+    ap.add_argument("--config", default="cfg3")
+    ap.add_argument("--envs", type=int, default=4)
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=3, help="env-steps of random actions before rendering")
+    ap.add_argument("--substeps", type=int, default=20)
+    ap.add_argument("--track", default=None, help="body name the camera follows")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", required=True)
+    a = ap.parse_args(argv)
+    from .sim import BatchSim
+    m = load_config(a.config)
+    rng = np.random.default_rng(a.seed)
+    sim = BatchSim(m, a.envs)
+    sim.reset()
+    lo, hi = m.act_ctrlrange[:, 0], m.act_ctrlrange[:, 1]
+    for _ in range(a.steps):
+        sim.step(rng.uniform(lo, hi, (a.envs, m.nu)), a.substeps)
+    cam = default_camera(m, m.body_id(a.track) if a.track else -1)
+    rgb, depth, seg = sim.render(a.size, a.size, cam, rgb=True, depth=True, segmentation=True)
+    out = Path(a.out)
+    out.mkdir(parents=True, exist_ok=True)
+    for e in range(a.envs):
+        write_ppm(out / f"env{e:03d}.ppm", rgb[e])
+    np.savez_compressed(out / "depth_seg.npz", depth=depth, seg=seg)
+    names = m.names["geom"]
+    ids, counts = np.unique(seg[0], return_counts=True)
+    print(f"wrote {a.envs} images of {a.size}x{a.size} to {out}; env 0 pixels per geom: " +
+          ", ".join(f"{names[i] if i >= 0 else 'background'}={c}" for i, c in zip(ids, counts)))
+    sim.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -38,6 +38,7 @@ EXPORTS = [
     "hsr_batch_set_profiling", "hsr_batch_last_timing", "hsr_batch_set_graph", "hsr_batch_set_persistent", "hsr_batch_is_persistent",
     "hsr_batch_obs_openai", "hsr_batch_obs_openai_dev", "hsr_batch_set_debug", "hsr_batch_cap_counts", "hsr_batch_cap_histogram", "hsr_batch_newton_trips", "hsr_batch_packing", "hsr_batch_set_schedule", "hsr_batch_set_solo", "hsr_batch_solo_handovers", "hsr_batch_set_goals",
     "hsr_batch_phase_cycles", "hsr_batch_block_times", "hsr_batch_kernel_times", "hsr_batch_set_queue", "hsr_batch_set_mpr_warm",
+    "hsr_model_hull_planes", "hsr_batch_render", "hsr_batch_render_dev",
 ]
 
 F_XPOS, F_XMAT, F_M, F_QACC, F_QACC_SMOOTH, F_QFRC_SMOOTH, F_QFRC_CONSTRAINT, F_NCON, F_NEFC, F_CONTACT, F_NITER = range(11)
@@ -102,6 +103,9 @@ def load_library():
     L.hsr_batch_packing.argtypes = [vp, C.POINTER(C.c_int32)]
     L.hsr_batch_set_solo.argtypes = [vp, C.c_int, C.c_float]
     L.hsr_batch_solo_handovers.argtypes = [vp, C.POINTER(C.c_int)]
+    L.hsr_model_hull_planes.argtypes = [vp, C.c_int, fp, C.c_int]
+    L.hsr_batch_render.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, fp, u8p, fp, i32p]
+    L.hsr_batch_render_dev.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, fp, vp, vp, vp]
     _lib = L
     return L
 
@@ -236,6 +240,44 @@ class BatchSim:
 
     def obs_openai_dev(self, d_out, ids=None):
         _check(self._L, self._L.hsr_batch_obs_openai_dev(self._b, ids or self.openai_ids(), C.c_void_p(int(d_out))))
+
+    def _render_args(self, camera, geom_rgba):
+        from .render import default_camera
+        cam = camera if camera is not None else default_camera(self.model)
+        pal = None if geom_rgba is None else _f32(geom_rgba, (self.model.ngeom, 4))
+        return cam.as_array(), int(cam.track_body), pal
+
+    def render(self, width, height, camera=None, rgb=True, depth=False, segmentation=False, geom_rgba=None):
+        """Images of every env from one camera (include/hsrsim.h: hsr_batch_render) -> the requested ones of
+        rgb uint8 [N,H,W,3], depth float32 [N,H,W] (distance along the camera axis; zfar on background), segmentation int32 [N,H,W]
+        (geom id, -1 on background), in that order; a single array when one is requested.  camera: render.Camera (None: the
+        model's default_camera); geom_rgba: [ngeom,4] colours (None: render.default_palette).  Poses of the last reset / forward / step."""
+        cam, track, pal = self._render_args(camera, geom_rgba)
+        w, h = int(width), int(height)
+        ok = 1 <= w <= 4096 and 1 <= h <= 4096
+        o_rgb = np.empty((self.n, h, w, 3), np.uint8) if rgb and ok else None
+        o_dep = np.empty((self.n, h, w), np.float32) if depth and ok else None
+        o_seg = np.empty((self.n, h, w), np.int32) if segmentation and ok else None
+        _check(self._L, self._L.hsr_batch_render(self._b, _fp(cam), track, w, h, _fp(pal),
+                                                 None if o_rgb is None else o_rgb.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(o_dep),
+                                                 None if o_seg is None else o_seg.ctypes.data_as(C.POINTER(C.c_int32))))
+        outs = [o for o, want in ((o_rgb, rgb), (o_dep, depth), (o_seg, segmentation)) if want]
+        return outs[0] if len(outs) == 1 else tuple(outs)
+
+    def render_dev(self, width, height, camera=None, rgb=None, depth=None, segmentation=None, geom_rgba=None):
+        """render() into caller-provided torch tensors on the batch's device (uint8 [N,H,W,3], float32 [N,H,W], int32 [N,H,W];
+        None skips an output); asynchronous on the batch stream (stream_ptr)."""
+        cam, track, pal = self._render_args(camera, geom_rgba)
+        w, h = int(width), int(height)
+        for t, shape, dt in ((rgb, (self.n, h, w, 3), "torch.uint8"), (depth, (self.n, h, w), "torch.float32"),
+                             (segmentation, (self.n, h, w), "torch.int32")):
+            if t is not None:
+                if tuple(t.shape) != shape or str(t.dtype) != dt or not t.is_contiguous() or t.device.type != "cuda":
+                    raise AssertionError(f"render_dev: expected a contiguous {dt} tensor of shape {shape} on the GPU")
+                if t.device.index != self.device:
+                    raise AssertionError(f"render_dev: tensor on cuda:{t.device.index}, the batch is on cuda:{self.device}")
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _check(self._L, self._L.hsr_batch_render_dev(self._b, _fp(cam), track, w, h, _fp(pal), ptr(rgb), ptr(depth), ptr(segmentation)))
 
     def bad_state(self):
         out = np.empty(self.n, np.uint8)

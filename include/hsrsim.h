@@ -46,6 +46,9 @@ int hsr_model_ctrlrange(const hsr_model *m, float *out /*[nu,2]*/); /* model.act
 int hsr_model_qpos0(const hsr_model *m, float *out /*[nq]*/);       /* sim.data.qpos after MjSim() (hsr/mujoco_env.py:49) */
 int hsr_model_body_id(const hsr_model *m, const char *name);       /* name lookup behind data.get_body_xpos (hsr/env.py:144,180,184) */
 int hsr_model_joint_qpos_addr(const hsr_model *m, const char *name, int *start, int *end); /* model.get_joint_qpos_addr (hsr/env.py:153) */
+/* face planes (n, w), n.x <= w inside, of a mesh geom's convex hull in the geom frame (computed in double from the hull vertices on
+ * first use; coplanar facets merged).  Writes min(count, cap) planes and returns the count, or HSR_EINVAL for a geom that is not a mesh. */
+int hsr_model_hull_planes(const hsr_model *m, int geom, float *out /*[cap,4]*/, int cap);
 
 /* ---- batch of N independent envs on one GPU: replaces N x mujoco_py.MjSim(model) (hsr/mujoco_env.py:34) */
 int hsr_batch_create(const hsr_model *m, int n_envs, int device_id, hsr_batch **out);
@@ -98,6 +101,18 @@ int hsr_batch_body_xpos(hsr_batch *b, int body_id, float *out /*[N,3]*/);
  * joints, dof address of the two finger joints}.  Positions / velocities are those of the last forward pass. */
 int hsr_batch_obs_openai(hsr_batch *b, const int *ids, float *out /*[N,25]*/);
 int hsr_batch_obs_openai_dev(hsr_batch *b, const int *ids, float *d_out);
+/* render (hsr/mujoco_env.py:105-125, batched): cam[9] = lookat3 distance azimuth elevation (degrees) fovy (degrees) znear zfar,
+ * MuJoCo free-camera convention; track_body >= 0: per-env lookat = xpos(track_body) + lookat. geom_rgba [ngeom,4] or NULL
+ * (the model's default palette). Outputs may be NULL. Poses are those of the last reset / forward / step.
+ * A ray caster over the collision geoms (the blob carries no visual-only geoms): rgb uint8 [N,H,W,3], depth float [N,H,W] (distance
+ * along the camera axis, zfar on background), segid int32 [N,H,W] (geom id, -1 on background); row 0 is the top of the image.
+ * Shading: rgb = rgba.rgb (0.1 + 0.4 max(0, n.v) + 0.5 max(0, n.z)), clamped, no shadows / specular / textures.
+ * Never writes simulation state.  HSR_EINVAL: width / height outside 1..4096, a non-finite camera, fovy outside (0, 180),
+ * znear <= 0 or zfar <= znear, a track_body out of range or the mocap body. */
+int hsr_batch_render(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
+                     uint8_t *rgb /*[N,H,W,3]*/, float *depth /*[N,H,W]*/, int32_t *segid /*[N,H,W]*/);
+int hsr_batch_render_dev(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
+                         uint8_t *d_rgb, float *d_depth, int32_t *d_segid);   /* asynchronous on hsr_batch_stream() */
 /* per-env error flags (non-finite or |q| > 1e10), the batched form of MuJoCo's mj_checkPos/Vel */
 int hsr_batch_bad_state(hsr_batch *b, uint8_t *out /*[N]*/);
 
