@@ -279,7 +279,11 @@ extern "C" int hsr_model_hull_planes(const hsr_model *m, int geom, float *out, i
 
 // ------------------------------------------------------------------ batch
 typedef void (*persist_fn)(const DevModel *, DevState, int, int, float, int, StepIO);
-struct GraphKey { int nsub, goal_body; float geofence; bool operator<(const GraphKey &o) const { return std::tie(nsub, goal_body, geofence) < std::tie(o.nsub, o.goal_body, o.geofence); } };
+// the chain's captured graphs hold the capture launches too (period, slots, buffer)
+struct GraphKey {
+    int nsub, goal_body; float geofence; int cap_every, cap_n; const void *cap;
+    bool operator<(const GraphKey &o) const { return std::tie(nsub, goal_body, geofence, cap_every, cap_n, cap) < std::tie(o.nsub, o.goal_body, o.geofence, o.cap_every, o.cap_n, o.cap); }
+};
 
 struct hsr_batch {
     const hsr_model *model = nullptr;
@@ -331,6 +335,15 @@ struct hsr_batch {
     std::vector<float> rgba_host;  // what d_rgba holds
     void *d_rimg = nullptr;        // staging of the host variant: rgb | depth | segid
     size_t rimg_bytes = 0;
+    // in-step frame capture (hsr_batch_set_capture): every cap_every substeps, the poses of the envs in the cap_n slots (model.h: StepIO::cap)
+    int cap_every = 0, cap_n = 0;  // cap_every = 0: off
+    CaptureDesc *d_cap_desc = nullptr;     // what the persistent kernel reads (model.h)
+    int *d_cap_slot = nullptr;     // [N] slot of every env, -1: none
+    int *d_cap_env = nullptr;      // [HSR_CAPTURE_MAX] env of every slot
+    int *d_cap_cnt = nullptr;      // [HSR_CAPTURE_MAX] frames of every slot in the last step
+    float *d_cap = nullptr;        // [rows][12 nlink][cap_n]: the frames of the last step, its final poses in the last row
+    size_t cap_floats = 0;
+    int cap_rows = 0;              // rows of the last step (frames of its longest possible run + the final one); 0: none since the last set_capture
 };
 
 // global copies of the two constant LDS tables of the persistent kernel (same packing: kin2.h)
@@ -915,6 +928,7 @@ extern "C" void hsr_batch_destroy(hsr_batch *b) {
     for (auto &kv : b->graphs) hipGraphExecDestroy(kv.second);
     for (void *p : b->allocs) hipFree(p);
     if (b->d_rimg) hipFree(b->d_rimg);
+    if (b->d_cap) hipFree(b->d_cap);
     for (hipEvent_t ev : b->kev) hipEventDestroy(ev);
     for (auto &pr : b->klog) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     if (b->ev0) hipEventDestroy(b->ev0);
@@ -1057,11 +1071,26 @@ extern "C" int hsr_batch_packing(hsr_batch *b, int32_t *out) {
 }
 
 // one substep of the per-substep chain = 4 launches on the batch stream (the persistent kernel needs none of them)
-static void launch_substep(hsr_batch *b, int mode, int goal_body, float geofence, int debug, hipStream_t st, bool timed) {
+// Frame capture outside the persistent kernel (hsr_batch_set_capture): lane = (pose row, slot); frame `frame` of every slot gets its env's
+// xpos / xmat - on the chain's capture substeps right after k_kinematics, for the envs still live (not done: k_kinematics has just written
+// their poses), and at the end of every step as the slot's final frame, with the slot's frame count (from nsteps: the substeps it ran)
+__global__ void k_capture(DevState s, int nlink, const int *cap_env, int R, float *cap, int frame, int live_only, int every, int *cnt) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 12 * nlink * R) return;
+    const int row = i / R, r = i % R, e = cap_env[r];
+    if (live_only && s.done[e]) return;
+    cap[(size_t)frame * 12 * nlink * R + i] = row < 3 * nlink ? s.xpos[(size_t)row * s.N + e] : s.xmat[(size_t)(row - 3 * nlink) * s.N + e];
+    if (cnt && row == 0) { const int n = s.nsteps[e]; cnt[r] = n == 0 ? 0 : (n - 1) / every + 1; }
+}
+
+static void launch_substep(hsr_batch *b, int mode, int goal_body, float geofence, int debug, hipStream_t st, bool timed, int sub = -1) {
     const int N = b->N;
     auto rec = [&](void) { if (timed) { hipEvent_t ev; hipEventCreate(&ev); hipEventRecord(ev, st); b->kev.push_back(ev); } };
     rec();
     hipLaunchKernelGGL(k_kinematics, dim3((N + 63) / 64), dim3(64), (size_t)64 * (b->ds.kstride + 24 * b->dm.nlink + 1) * sizeof(float), st, b->dm, b->ds);
+    if (sub >= 0 && b->cap_every > 0 && sub % b->cap_every == 0)
+        hipLaunchKernelGGL(k_capture, grid1((size_t)12 * b->dm.nlink * b->cap_n), dim3(256), 0, st, b->ds, b->dm.nlink, (const int *)b->d_cap_env, b->cap_n, b->d_cap,
+                           sub / b->cap_every, 1, b->cap_every, (int *)nullptr);
     rec();
     if (b->dm.npair > 0) {
         hipLaunchKernelGGL(k_cull, dim3((N + 63) / 64, (b->dm.npair + b->pairs_per_wave - 1) / b->pairs_per_wave), dim3(64), 0, st, b->dm, b->ds);
@@ -1257,6 +1286,19 @@ extern "C" int hsr_batch_step_dev(hsr_batch *b, const float *d_ctrl, int n_subst
         HIPCHK(hipEventRecord(b->ev0, st));
     }
     const bool fused = b->persist && n_substeps > 0;      // the persistent kernel reads ctrl and writes obs / reward / done / nsteps itself
+    const int cap_rows = b->cap_every > 0 ? (n_substeps > 0 ? (n_substeps - 1) / b->cap_every + 1 : 0) + 1 : 0;
+    if (cap_rows > 0) {
+        const size_t need = (size_t)cap_rows * 12 * b->dm.nlink * b->cap_n;
+        if (need > b->cap_floats) {                       // grown after the stream has let go of the old buffer
+            HIPCHK(hipStreamSynchronize(st));
+            if (b->d_cap) { HIPCHK(hipFree(b->d_cap)); b->d_cap = nullptr; b->cap_floats = 0; }
+            HIPCHK(hipMalloc(&b->d_cap, need * sizeof(float)));
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)b->d_cap, 0x7fc00000, need, st));      // a new buffer holds NaN
+            b->cap_floats = need;
+            const CaptureDesc cd{b->d_cap, b->d_cap_slot, b->cap_every, b->cap_n};
+            HIPCHK(hipMemcpy(b->d_cap_desc, &cd, sizeof cd, hipMemcpyHostToDevice));
+        }
+    }
     if (!fused) hipLaunchKernelGGL(k_begin_step, grid1(N), dim3(256), 0, st, b->ds, d_ctrl, b->dm.nu);
     if (fused) {
         const int epb = 64 / b->group;
@@ -1270,7 +1312,7 @@ extern "C" int hsr_batch_step_dev(hsr_batch *b, const float *d_ctrl, int n_subst
         if (sched) hipLaunchKernelGGL(k_schedule, dim3((N + SCHED_CHUNK - 1) / SCHED_CHUNK), dim3(1024), 0, st, b->ds, epb, b->d_slot_env);
         DevState dsl = b->ds;
         dsl.slot_env = sched ? b->d_slot_env : nullptr;
-        const StepIO io{d_ctrl, d_obs, d_reward, d_done, d_nsteps};
+        const StepIO io{d_ctrl, d_obs, d_reward, d_done, d_nsteps, b->cap_every > 0 ? b->d_cap_desc : nullptr};
         // more tasks than the GPU holds workgroups at once: persistent workgroups + the work queue (persist.h), else one task per workgroup
         const int T = (N + epb - 1) / epb;
         int chunk = b->queue_chunk;
@@ -1300,12 +1342,12 @@ extern "C" int hsr_batch_step_dev(hsr_batch *b, const float *d_ctrl, int n_subst
         if (b->kernel_log) { hipEventRecord(k1, st); b->klog.push_back({k0, k1}); }
         if (b->profiling) { hipEvent_t ev; hipEventCreate(&ev); hipEventRecord(ev, st); b->kev.push_back(ev); }   // slots 0,1 empty; slot 2 = the persistent kernel
     } else if (b->use_graph && !b->profiling && n_substeps > 0) {
-        GraphKey key{n_substeps, goal_body, geofence};
+        GraphKey key{n_substeps, goal_body, geofence, b->cap_every, b->cap_n, b->d_cap};
         auto it = b->graphs.find(key);
         if (it == b->graphs.end()) {
             hipGraph_t graph;
             HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            for (int i = 0; i < n_substeps; i++) launch_substep(b, 1, goal_body, geofence, 0, st, false);
+            for (int i = 0; i < n_substeps; i++) launch_substep(b, 1, goal_body, geofence, 0, st, false, i);
             HIPCHK(hipStreamEndCapture(st, &graph));
             hipGraphExec_t exec;
             HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
@@ -1315,7 +1357,7 @@ extern "C" int hsr_batch_step_dev(hsr_batch *b, const float *d_ctrl, int n_subst
         }
         HIPCHK(hipGraphLaunch(it->second, st));
     } else {
-        for (int i = 0; i < n_substeps; i++) launch_substep(b, 1, goal_body, geofence, 0, st, b->profiling);
+        for (int i = 0; i < n_substeps; i++) launch_substep(b, 1, goal_body, geofence, 0, st, b->profiling, i);
     }
     if (!fused) {
         if (d_obs) {
@@ -1325,6 +1367,10 @@ extern "C" int hsr_batch_step_dev(hsr_batch *b, const float *d_ctrl, int n_subst
         }
         hipLaunchKernelGGL(k_end_step, grid1(N), dim3(256), 0, st, b->ds, d_reward, d_done, d_nsteps);
     }
+    if (cap_rows > 0)       // the final frame (the poses after the step: the reference's 50 closing frames show them, hsr/env.py:128-130) and the counts
+        hipLaunchKernelGGL(k_capture, grid1((size_t)12 * b->dm.nlink * b->cap_n), dim3(256), 0, st, b->ds, b->dm.nlink, (const int *)b->d_cap_env, b->cap_n, b->d_cap,
+                           cap_rows - 1, 0, b->cap_every, b->d_cap_cnt);
+    b->cap_rows = cap_rows;
     HIPCHK(hipGetLastError());
     if (b->profiling) {
         HIPCHK(hipEventRecord(b->ev1, st));
@@ -1489,9 +1535,12 @@ static void default_palette(const hsr_model *m, std::vector<float> &out) {
     }
 }
 
+// frames = false: one image per env from the state's poses (hsr_batch_render); true: one per (slot, row) of the captured frames of the last
+// step (hsr_batch_render_frames), rows of the slots without a frame there skipped
 static int render_launch(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
-                         uint8_t *d_rgb, float *d_depth, int32_t *d_segid) {
+                         uint8_t *d_rgb, float *d_depth, int32_t *d_segid, bool frames = false) {
     NULLCHK(b);
+    if (frames && (b->cap_every <= 0 || b->cap_rows <= 0)) return fail(HSR_EINVAL, "render_frames: no captured step (hsr_batch_set_capture, then a step)");
     if (!cam) return fail(HSR_EINVAL, "render: null camera");
     if (width < 1 || width > 4096 || height < 1 || height > 4096) return fail(HSR_EINVAL, "render: width and height must be in 1..4096");
     for (int k = 0; k < 9; k++) if (!std::isfinite(cam[k])) return fail(HSR_EINVAL, "render: non-finite camera");
@@ -1536,11 +1585,13 @@ static int render_launch(hsr_batch *b, const float *cam, int track_body, int wid
     c.W = width; c.H = height; c.tiles_x = (width + 15) / 16; c.ntiles = c.tiles_x * ((height + 15) / 16);
     const size_t lds = ((size_t)RREC * d.ngeom + 4) * sizeof(float);
     const int per_launch = std::max(1, (1 << 30) / c.ntiles);          // grid.x stays below 2^31
-    for (int e0 = 0; e0 < b->N; e0 += per_launch) {
+    const int nimg = frames ? b->cap_n * b->cap_rows : b->N;
+    const FrameSrc fs{b->d_cap, b->d_cap_cnt, b->cap_n, b->cap_rows};
+    for (int e0 = 0; e0 < nimg; e0 += per_launch) {
         c.env0 = e0;
-        const int ne = std::min(per_launch, b->N - e0);
-        hipLaunchKernelGGL(k_render, dim3((unsigned)(ne * c.ntiles)), dim3(256), lds, b->stream, b->dm, b->ds, c, (const float4 *)b->d_planes,
-                           (const int2 *)b->d_prange, (const float4 *)b->d_rgba, d_rgb, d_depth, d_segid);
+        const int ne = std::min(per_launch, nimg - e0);
+        hipLaunchKernelGGL(frames ? k_render<true> : k_render<false>, dim3((unsigned)(ne * c.ntiles)), dim3(256), lds, b->stream, b->dm, b->ds, c, (const float4 *)b->d_planes,
+                           (const int2 *)b->d_prange, (const float4 *)b->d_rgba, d_rgb, d_depth, d_segid, fs);
     }
     HIPCHK(hipGetLastError());
     return HSR_OK;
@@ -1549,10 +1600,11 @@ extern "C" int hsr_batch_render_dev(hsr_batch *b, const float *cam, int track_bo
                                     uint8_t *d_rgb, float *d_depth, int32_t *d_segid) {
     return render_launch(b, cam, track_body, width, height, geom_rgba, d_rgb, d_depth, d_segid);
 }
-extern "C" int hsr_batch_render(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
-                                uint8_t *rgb, float *depth, int32_t *segid) {
+static int render_host(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
+                       uint8_t *rgb, float *depth, int32_t *segid, bool frames) {
     NULLCHK(b);
-    const size_t npx = (size_t)b->N * (size_t)std::max(width, 0) * (size_t)std::max(height, 0);
+    const size_t nimg = frames ? (size_t)b->cap_n * b->cap_rows : (size_t)b->N;
+    const size_t npx = nimg * (size_t)std::max(width, 0) * (size_t)std::max(height, 0);
     const size_t o_depth = (3 * npx + 15) & ~(size_t)15, o_seg = o_depth + 4 * npx, bytes = o_seg + 4 * npx;
     if (width >= 1 && width <= 4096 && height >= 1 && height <= 4096 && bytes > b->rimg_bytes) {
         HIPCHK(hipSetDevice(b->device));
@@ -1562,12 +1614,90 @@ extern "C" int hsr_batch_render(hsr_batch *b, const float *cam, int track_body, 
         b->rimg_bytes = bytes;
     }
     uint8_t *base = (uint8_t *)b->d_rimg;
+    if (frames && npx > 0) {      // frames that are not rendered keep what the caller's arrays hold
+        if (rgb) HIPCHK(hipMemcpyAsync(base, rgb, 3 * npx, hipMemcpyHostToDevice, b->stream));
+        if (depth) HIPCHK(hipMemcpyAsync(base + o_depth, depth, 4 * npx, hipMemcpyHostToDevice, b->stream));
+        if (segid) HIPCHK(hipMemcpyAsync(base + o_seg, segid, 4 * npx, hipMemcpyHostToDevice, b->stream));
+    }
     int rc = render_launch(b, cam, track_body, width, height, geom_rgba, rgb ? base : nullptr, depth ? (float *)(base + o_depth) : nullptr,
-                           segid ? (int32_t *)(base + o_seg) : nullptr);
+                           segid ? (int32_t *)(base + o_seg) : nullptr, frames);
     if (rc) return rc;
     if (rgb) HIPCHK(hipMemcpyAsync(rgb, base, 3 * npx, hipMemcpyDeviceToHost, b->stream));
     if (depth) HIPCHK(hipMemcpyAsync(depth, base + o_depth, 4 * npx, hipMemcpyDeviceToHost, b->stream));
     if (segid) HIPCHK(hipMemcpyAsync(segid, base + o_seg, 4 * npx, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return HSR_OK;
+}
+extern "C" int hsr_batch_render(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
+                                uint8_t *rgb, float *depth, int32_t *segid) {
+    return render_host(b, cam, track_body, width, height, geom_rgba, rgb, depth, segid, false);
+}
+
+// ------------------------------------------------------------------ in-step frame capture (hsr/env.py:118-131: the recorder's capture_frame
+// every record_freq substeps, before sim.step(), and 50 more frames of the final poses when the goal is reached)
+extern "C" int hsr_batch_set_capture(hsr_batch *b, int every, int n, const int *env_ids) {
+    NULLCHK(b);
+    if (every < 0) return fail(HSR_EINVAL, "set_capture: every >= 0");
+    if (every > 0) {
+        if (n < 1 || n > HSR_CAPTURE_MAX || !env_ids) return fail(HSR_EINVAL, "set_capture: 1..HSR_CAPTURE_MAX envs");
+        std::vector<int> slot(b->N, -1);
+        for (int r = 0; r < n; r++) {
+            if (env_ids[r] < 0 || env_ids[r] >= b->N) return fail(HSR_EINVAL, "set_capture: env id out of range");
+            if (slot[env_ids[r]] >= 0) return fail(HSR_EINVAL, "set_capture: env ids must be distinct");
+            slot[env_ids[r]] = r;
+        }
+        HIPCHK(hipSetDevice(b->device));
+        HIPCHK(hipStreamSynchronize(b->stream));          // a step in flight still reads the old tables
+        int rc;
+        if (!b->d_cap_slot) {
+            if ((rc = dalloc(b, &b->d_cap_desc, 1)) || (rc = dalloc(b, &b->d_cap_slot, (size_t)b->N)) || (rc = dalloc(b, &b->d_cap_env, (size_t)HSR_CAPTURE_MAX)) || (rc = dalloc(b, &b->d_cap_cnt, (size_t)HSR_CAPTURE_MAX))) return rc;
+        }
+        HIPCHK(hipMemcpy(b->d_cap_slot, slot.data(), sizeof(int) * b->N, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b->d_cap_env, env_ids, sizeof(int) * n, hipMemcpyHostToDevice));
+        const CaptureDesc cd{b->d_cap, b->d_cap_slot, every, n};
+        HIPCHK(hipMemcpy(b->d_cap_desc, &cd, sizeof cd, hipMemcpyHostToDevice));
+        if (b->d_cap) {                                   // frames of earlier settings: NaN
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)b->d_cap, 0x7fc00000, b->cap_floats, b->stream));
+            HIPCHK(hipStreamSynchronize(b->stream));
+        }
+    }
+    b->cap_every = every;
+    b->cap_n = every > 0 ? n : 0;
+    b->cap_rows = 0;
+    return HSR_OK;
+}
+extern "C" int hsr_batch_capture_counts(hsr_batch *b, int32_t *counts) {
+    NULLCHK(b);
+    if (b->cap_every <= 0 || b->cap_rows <= 0) return fail(HSR_EINVAL, "capture_counts: no captured step (hsr_batch_set_capture, then a step)");
+    HIPCHK(hipSetDevice(b->device));
+    if (counts) HIPCHK(hipMemcpyAsync(counts, b->d_cap_cnt, sizeof(int32_t) * b->cap_n, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return b->cap_rows;
+}
+extern "C" int hsr_batch_capture_poses(hsr_batch *b, float *xpos, float *xmat) {
+    NULLCHK(b);
+    if (b->cap_every <= 0 || b->cap_rows <= 0) return fail(HSR_EINVAL, "capture_poses: no captured step (hsr_batch_set_capture, then a step)");
+    HIPCHK(hipSetDevice(b->device));
+    const int R = b->cap_n, rows = b->cap_rows, nl = b->dm.nlink;
+    std::vector<float> h((size_t)rows * 12 * nl * R);
+    HIPCHK(hipMemcpyAsync(h.data(), b->d_cap, h.size() * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    for (int r = 0; r < R; r++)
+        for (int k = 0; k < rows; k++) {
+            const float *f = h.data() + (size_t)k * 12 * nl * R + r;
+            const size_t o = (size_t)r * rows + k;
+            if (xpos) for (int i = 0; i < 3 * nl; i++) xpos[o * 3 * nl + i] = f[(size_t)i * R];
+            if (xmat) for (int i = 0; i < 9 * nl; i++) xmat[o * 9 * nl + i] = f[(size_t)(3 * nl + i) * R];
+        }
+    return HSR_OK;
+}
+extern "C" int hsr_batch_render_frames_dev(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
+                                           uint8_t *d_rgb, float *d_depth, int32_t *d_segid) {
+    return render_launch(b, cam, track_body, width, height, geom_rgba, d_rgb, d_depth, d_segid, true);
+}
+extern "C" int hsr_batch_render_frames(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
+                                       uint8_t *rgb, float *depth, int32_t *segid) {
+    NULLCHK(b);
+    if (b->cap_every <= 0 || b->cap_rows <= 0) return fail(HSR_EINVAL, "render_frames: no captured step (hsr_batch_set_capture, then a step)");
+    return render_host(b, cam, track_body, width, height, geom_rgba, rgb, depth, segid, true);
 }

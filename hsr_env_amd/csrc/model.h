@@ -41,9 +41,13 @@ struct DevModel {
     int nldsv;
 };
 
+// In-step frame capture (hsr_batch_set_capture), in device memory so that the persistent kernel holds one pointer, not four fields, over
+// its whole launch: slot[e] = capture slot of env e or -1; frame k of slot r holds the link poses of substep k * every at
+// cap[(k * 12 nlink + i) * R + r], i over the 3 nlink xpos rows, then the 9 nlink xmat rows
+struct CaptureDesc { float *cap; const int *slot; int every, R; };
 // env-step inputs / outputs of the caller (hsr_batch_step_dev), env-major as the C-ABI hands them over: the persistent kernel reads ctrl
 // and writes obs / reward / done / nsteps itself (ctrl == NULL: the state arrays s.ctrl / s.done are used as they are)
-struct StepIO { const float *ctrl; float *obs, *reward; uint8_t *done; int32_t *nsteps; };
+struct StepIO { const float *ctrl; float *obs, *reward; uint8_t *done; int32_t *nsteps; const CaptureDesc *cap; };      // cap == NULL: no capture
 
 // per-batch buffers; every array is [rows][N] with the env index fastest (coalesced across lanes)
 struct DevState {

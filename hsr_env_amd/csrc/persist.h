@@ -352,6 +352,17 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
             for (int i = c; i < 9 * m.nlink; i += G) s.xmat[(size_t)i * N + e] = poseL[12 * (i / 9) + i % 9];
             for (int i = c; i < 6 * m.nlink; i += G) { const int l = (i % (3 * m.nlink)) / 3; s.lvel[(size_t)i * N + e] = recL[12 * l + (i < 3 * m.nlink ? 0 : 3) + i % 3]; }   // link w, then v(origin)
         }
+        // in-step frame capture (StepIO::cap): a live env's poses of this substep's forward pass every `every` substeps - what the
+        // reference's recorder grabs before sim.step() (hsr/env.py:118-121); `sub` is the env-step's substep in every mode
+        if (io.cap && valid && (!REP || g == 0)) {
+            const CaptureDesc cd = *io.cap;
+            const int slot = sub % cd.every == 0 ? cd.slot[e] : -1;
+            if (slot >= 0) {
+                float *f = cd.cap + (size_t)(sub / cd.every) * 12 * m.nlink * cd.R + slot;
+                for (int i = c; i < 3 * m.nlink; i += G) f[(size_t)i * cd.R] = poseL[12 * (i / 3) + 9 + i % 3];
+                for (int i = c; i < 9 * m.nlink; i += G) f[(size_t)(3 * m.nlink + i) * cd.R] = poseL[12 * (i / 9) + i % 9];
+            }
+        }
         PHASE_K(31);
         // ---------------- C: collision
         // G: lane = geom, world placement of every geom once per substep (LDS, next to the link poses)

@@ -1,5 +1,6 @@
 // k_render: batched ray caster over the collision geoms (include/hsrsim.h: hsr_batch_render).  Read-only on the simulation state:
-// it reads the link poses of the last reset / forward / step (DevState::xpos / xmat) and writes nothing but its three images.
+// it reads the link poses of the last reset / forward / step (DevState::xpos / xmat) - or, k_render<true>, captured frames of the last
+// step (hsr_batch_render_frames) - and writes nothing but its three images.
 //
 // Layout: one 256-thread workgroup (4 waves) renders one 16 x 16 pixel tile of one env, one lane per pixel; grid = envs x tiles.
 // Prologue (wave 0): every geom's world placement from its link pose, culled by its bounding sphere (geom_rbound around the geom
@@ -46,19 +47,30 @@ __device__ __forceinline__ void slab(v3 o, v3 inv, const float *c, const float *
     }
 }
 
+// FR (hsr_batch_render_frames): the poses come from the captured frames instead of the state - image i = slot i / rows, frame i % rows
+// of the capture buffer (model.h: StepIO::cap); a frame at or past its slot's count, other than the last (final) one, is not rendered
+struct FrameSrc { const float *cap; const int *cnt; int R, rows; };
+
+template <bool FR>
 __global__ void __launch_bounds__(256) k_render(DevModel m, DevState s, RenderCam c, const float4 *__restrict__ planes,
-                                                const int2 *__restrict__ prange, const float4 *__restrict__ rgba, uint8_t *rgb, float *depth, int32_t *segid) {
+                                                const int2 *__restrict__ prange, const float4 *__restrict__ rgba, uint8_t *rgb, float *depth, int32_t *segid,
+                                                FrameSrc fs) {
     extern __shared__ float rrec[];                       // [ngeom][RREC] candidates, then the candidate count
     const int tid = threadIdx.x, lane = tid & 63;
-    const int tile = blockIdx.x % c.ntiles, e = c.env0 + blockIdx.x / c.ntiles, N = s.N;
+    const int tile = blockIdx.x % c.ntiles, e = c.env0 + blockIdx.x / c.ntiles, N = s.N;      // e: the image (FR: slot x frame)
     const int x0 = (tile % c.tiles_x) * 16, y0 = (tile / c.tiles_x) * 16;
     const v3 fwd = mk3(c.fwd[0], c.fwd[1], c.fwd[2]), rt = mk3(c.right[0], c.right[1], c.right[2]), up = mk3(c.up[0], c.up[1], c.up[2]);
+    View xpos{s.xpos + e, N}, xmat{s.xmat + e, N};
+    if constexpr (FR) {
+        const int slot = e / fs.rows, k = e % fs.rows;
+        if (k < fs.rows - 1 && k >= fs.cnt[slot]) return;              // (whole workgroup)
+        float *p = const_cast<float *>(fs.cap) + (size_t)k * 12 * m.nlink * fs.R + slot;
+        xpos = View{p, fs.R}; xmat = View{p + (size_t)3 * m.nlink * fs.R, fs.R};
+    }
     // camera origin of this env
     v3 look = mk3(c.lookat[0], c.lookat[1], c.lookat[2]);
-    if (c.track_link >= 0) {
-        const View xpos{s.xpos + e, N}, xmat{s.xmat + e, N};
+    if (c.track_link >= 0)
         look = look + xpos.get3(c.track_link) + mulmv(xmat.getm(c.track_link), mk3(c.track_off[0], c.track_off[1], c.track_off[2]));
-    }
     const v3 cam = look - fwd * c.dist;
     int *ncand = reinterpret_cast<int *>(rrec + RREC * m.ngeom);
     if (tid < 64) {
@@ -78,7 +90,6 @@ __global__ void __launch_bounds__(256) k_render(DevModel m, DevState s, RenderCa
                 const v3 pg = ld3(m.geom_pos, g);
                 if (l == 0) { R = Rg; p = pg; }          // world link: identity pose
                 else {
-                    const View xpos{s.xpos + e, N}, xmat{s.xmat + e, N};
                     const m3 Rl = xmat.getm(l);
                     R = mulmm(Rl, Rg); p = xpos.get3(l) + mulmv(Rl, pg);
                 }

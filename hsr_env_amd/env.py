@@ -45,13 +45,14 @@ class VecHSREnv:
                  steps_per_action: int = 300, obs_type: str = None, render: bool = False, record: bool = False,
                  record_freq: int = None, render_freq: int = None, record_path: Path = None,
                  n_envs: int = 1, model: Optional[Model] = None, sim=None, device: int = 0,
-                 env_offset: int = 0, n_global: Optional[int] = None, block_space: Optional[Box] = None):
+                 env_offset: int = 0, n_global: Optional[int] = None, block_space: Optional[Box] = None,
+                 record_envs: Optional[List[int]] = None, record_size=None, record_camera=None):
         if model is None:
             model = load_config(str(xml_file)) if xml_file is not None else None
         if model is None:
             raise IOError("File %s does not exist" % xml_file)          # hsr/mujoco_env.py:30-31
-        if any([render, record, record_path, record_freq and False]):
-            raise NotImplementedError("rendering / recording are outside the batched hot path (camera-free obs)")
+        if any([render, render_freq]):
+            raise NotImplementedError("render=True / render_freq: the 'human' viewer needs a display (record=True writes videos)")
         if obs_type not in (None, "openai"):
             raise ValueError(f"unknown obs_type {obs_type!r}")
         if obs_type == "openai" and not ({"hand_l_proximal_joint", "hand_r_proximal_joint"} <= set(model.names["joint"]) and model.block_body()):
@@ -78,6 +79,19 @@ class VecHSREnv:
             from .sim import BatchSim
             sim = BatchSim(model, self.n_envs, device=device)
         self.sim = sim
+        # hsr/env.py:50-66: record when any of record / record_path / record_freq is given.  One video per recorded env (global ids
+        # record_envs, default [0]; a rank records the ones in its shard) under the directory record_path (record.py)
+        self._recorder = None
+        if any([record, record_path, record_freq]):
+            from .record import EnvRecorder
+            from .render import DEFAULT_SIZE, default_camera
+            gids = [int(g) for g in (record_envs if record_envs is not None else [0])]
+            if len(set(gids)) != len(gids) or any(g < 0 or g >= self.n_global for g in gids):
+                raise ValueError(f"record_envs must be distinct env ids in 0..{self.n_global - 1}")
+            mine = [g for g in gids if self.env_offset <= g < self.env_offset + self.n_envs]
+            self._recorder = EnvRecorder(sim, Path(record_path or "/tmp/training-video"), mine, [g - self.env_offset for g in mine],
+                                         self.record_freq, record_size or DEFAULT_SIZE,
+                                         record_camera if record_camera is not None else default_camera(model))
         bounds = model.act_ctrlrange.copy()
         self.action_space = Box(low=bounds[:, 0], high=bounds[:, 1], dtype=np.float32)
         self.init_qpos = model.qpos0.copy()
@@ -170,6 +184,8 @@ class VecHSREnv:
         rng = self._global_rng()
         self._reset_count += 1
         m = np.ones(self.n_envs, dtype=bool) if mask is None else np.asarray(mask, dtype=bool).reshape(self.n_envs)
+        if self._recorder is not None:
+            self._recorder.on_reset(m, self._time_steps > 0)
         self._time_steps[m] = 0
         if self.goals_specs:
             if self._extra_terms and self.goals is None:
@@ -219,6 +235,8 @@ class VecHSREnv:
                 from .sim import MujocoException
                 raise MujocoException(f"simulation diverged in env(s) {np.flatnonzero(bad)[:8].tolist()} (non-finite or |q| > 1e10)")
         self._time_steps += 1
+        if self._recorder is not None:
+            self._recorder.after_step(done, ns)
         if self._obs_type == "openai":
             obs = self.sim.obs_openai()
         self._last_obs = obs
@@ -262,6 +280,8 @@ class VecHSREnv:
         raise ValueError(f"unknown render mode {mode!r}")
 
     def close(self):
+        if getattr(self, "_recorder", None) is not None:
+            self._recorder.close()
         if getattr(self.sim, "close", None):
             self.sim.close()
 

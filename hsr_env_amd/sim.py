@@ -39,7 +39,10 @@ EXPORTS = [
     "hsr_batch_obs_openai", "hsr_batch_obs_openai_dev", "hsr_batch_set_debug", "hsr_batch_cap_counts", "hsr_batch_cap_histogram", "hsr_batch_newton_trips", "hsr_batch_packing", "hsr_batch_set_schedule", "hsr_batch_set_solo", "hsr_batch_solo_handovers", "hsr_batch_set_goals",
     "hsr_batch_phase_cycles", "hsr_batch_block_times", "hsr_batch_kernel_times", "hsr_batch_set_queue", "hsr_batch_set_mpr_warm",
     "hsr_model_hull_planes", "hsr_batch_render", "hsr_batch_render_dev",
+    "hsr_batch_set_capture", "hsr_batch_capture_counts", "hsr_batch_capture_poses", "hsr_batch_render_frames", "hsr_batch_render_frames_dev",
 ]
+
+CAPTURE_MAX = 1024          # include/hsrsim.h: HSR_CAPTURE_MAX
 
 F_XPOS, F_XMAT, F_M, F_QACC, F_QACC_SMOOTH, F_QFRC_SMOOTH, F_QFRC_CONSTRAINT, F_NCON, F_NEFC, F_CONTACT, F_NITER = range(11)
 
@@ -106,6 +109,11 @@ def load_library():
     L.hsr_model_hull_planes.argtypes = [vp, C.c_int, fp, C.c_int]
     L.hsr_batch_render.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, fp, u8p, fp, i32p]
     L.hsr_batch_render_dev.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, fp, vp, vp, vp]
+    L.hsr_batch_set_capture.argtypes = [vp, C.c_int, C.c_int, i32p]
+    L.hsr_batch_capture_counts.argtypes = [vp, i32p]
+    L.hsr_batch_capture_poses.argtypes = [vp, fp, fp]
+    L.hsr_batch_render_frames.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, fp, u8p, fp, i32p]
+    L.hsr_batch_render_frames_dev.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, fp, vp, vp, vp]
     _lib = L
     return L
 
@@ -278,6 +286,68 @@ class BatchSim:
                     raise AssertionError(f"render_dev: tensor on cuda:{t.device.index}, the batch is on cuda:{self.device}")
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         _check(self._L, self._L.hsr_batch_render_dev(self._b, _fp(cam), track, w, h, _fp(pal), ptr(rgb), ptr(depth), ptr(segmentation)))
+
+    # -- in-step frame capture (include/hsrsim.h: hsr_batch_set_capture; the recorder of hsr/env.py:118-131)
+    def set_capture(self, env_ids, every):
+        """Capture the link poses of the envs `env_ids` (slot r = env_ids[r]) every `every` substeps of each later step, before the
+        substep's dynamics, while the env is live; plus one final frame per slot with the poses after the step.  every = 0: off."""
+        ids = np.ascontiguousarray(np.atleast_1d(np.asarray(env_ids if every else [], dtype=np.int32)))
+        self._cap_n = len(ids) if every else 0
+        _check(self._L, self._L.hsr_batch_set_capture(self._b, int(every), len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32)) if len(ids) else None))
+
+    def capture_counts(self):
+        """Frames of every slot in the last step (the final frame not counted): int32 [n]."""
+        out = np.empty(max(getattr(self, "_cap_n", 0), 1), np.int32)
+        rc = self._L.hsr_batch_capture_counts(self._b, out.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc < 0:
+            _check(self._L, rc)
+        return out[:self._cap_n]
+
+    def capture_rows(self):
+        """Rows per slot of the last step: the frames of its longest possible run, then the final frame."""
+        rc = self._L.hsr_batch_capture_counts(self._b, None)
+        if rc < 0:
+            _check(self._L, rc)
+        return rc
+
+    def capture_poses(self):
+        """(xpos float32 [n, rows, nlink, 3], xmat [n, rows, nlink, 3, 3]) of the last step; row k < count: frame k, last row: the final frame."""
+        rows, nl = self.capture_rows(), self.model.nlink
+        xpos = np.empty((self._cap_n, rows, nl, 3), np.float32); xmat = np.empty((self._cap_n, rows, nl, 3, 3), np.float32)
+        _check(self._L, self._L.hsr_batch_capture_poses(self._b, _fp(xpos), _fp(xmat)))
+        return xpos, xmat
+
+    def render_frames(self, width, height, camera=None, rgb=True, depth=False, segmentation=False, geom_rgba=None):
+        """render() of the captured frames of the last step: rgb uint8 [n, rows, H, W, 3], depth float32 [n, rows, H, W], segmentation
+        int32 [n, rows, H, W] (the requested ones, in that order; a single array when one is requested); row k < capture_counts()[slot]
+        is frame k, the last row the final frame, the rows in between are zero (depth: NaN, segmentation: -2)."""
+        cam, track, pal = self._render_args(camera, geom_rgba)
+        w, h = int(width), int(height)
+        rows = self.capture_rows()
+        ok = 1 <= w <= 4096 and 1 <= h <= 4096
+        n = self._cap_n
+        o_rgb = np.zeros((n, rows, h, w, 3), np.uint8) if rgb and ok else None
+        o_dep = np.full((n, rows, h, w), np.nan, np.float32) if depth and ok else None
+        o_seg = np.full((n, rows, h, w), -2, np.int32) if segmentation and ok else None
+        _check(self._L, self._L.hsr_batch_render_frames(self._b, _fp(cam), track, w, h, _fp(pal),
+                                                        None if o_rgb is None else o_rgb.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(o_dep),
+                                                        None if o_seg is None else o_seg.ctypes.data_as(C.POINTER(C.c_int32))))
+        outs = [o for o, want in ((o_rgb, rgb), (o_dep, depth), (o_seg, segmentation)) if want]
+        return outs[0] if len(outs) == 1 else tuple(outs)
+
+    def render_frames_dev(self, width, height, camera=None, rgb=None, depth=None, segmentation=None, geom_rgba=None):
+        """render_frames() into caller-provided torch tensors on the batch's device (uint8 [n,rows,H,W,3], float32 [n,rows,H,W], int32
+        [n,rows,H,W]; None skips an output); the rows past a slot's count are left as they are.  Asynchronous on the batch stream."""
+        cam, track, pal = self._render_args(camera, geom_rgba)
+        w, h = int(width), int(height)
+        rows = self.capture_rows()
+        for t, shape, dt in ((rgb, (self._cap_n, rows, h, w, 3), "torch.uint8"), (depth, (self._cap_n, rows, h, w), "torch.float32"),
+                             (segmentation, (self._cap_n, rows, h, w), "torch.int32")):
+            if t is not None:
+                if tuple(t.shape) != shape or str(t.dtype) != dt or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != self.device:
+                    raise AssertionError(f"render_frames_dev: expected a contiguous {dt} tensor of shape {shape} on cuda:{self.device}")
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _check(self._L, self._L.hsr_batch_render_frames_dev(self._b, _fp(cam), track, w, h, _fp(pal), ptr(rgb), ptr(depth), ptr(segmentation)))
 
     def bad_state(self):
         out = np.empty(self.n, np.uint8)

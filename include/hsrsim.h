@@ -113,6 +113,31 @@ int hsr_batch_render(hsr_batch *b, const float *cam, int track_body, int width, 
                      uint8_t *rgb /*[N,H,W,3]*/, float *depth /*[N,H,W]*/, int32_t *segid /*[N,H,W]*/);
 int hsr_batch_render_dev(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
                          uint8_t *d_rgb, float *d_depth, int32_t *d_segid);   /* asynchronous on hsr_batch_stream() */
+/* In-step frame capture (hsr/env.py:118-131: VideoRecorder.capture_frame every record_freq substeps before sim.step(), 50 frames of the
+ * final poses after a step that reached the goal).  The n envs env_ids[0..n) get capture slots 0..n-1; every > 0 is the period in
+ * substeps, every = 0 turns capture off (the default; n and env_ids are then ignored).  In each later hsr_batch_step* a slot takes frame k
+ * at substep k * every if its env is live then (not done at an earlier substep of the step): the link poses of that substep's forward
+ * pass, what mujoco-py draws before sim.step().  An env that ran s substeps has s == 0 ? 0 : (s - 1) / every + 1 frames.  Each slot
+ * also gets a final frame: the poses after the step (HSR_F_XPOS / HSR_F_XMAT).  A step of S substeps keeps rows = (S == 0 ? 0 :
+ * (S - 1) / every + 1) + 1 rows per slot, the final frame in the last row; rows past a slot's count (other than the last) are not written.
+ * The frame buffer holds NaN when it is allocated and after every hsr_batch_set_capture with every > 0.
+ * Capture does not change any result of the step.  HSR_EINVAL: every < 0, n outside 1..HSR_CAPTURE_MAX, an env id out of range or
+ * repeated.  Synchronises. */
+#define HSR_CAPTURE_MAX 1024
+int hsr_batch_set_capture(hsr_batch *b, int every, int n, const int *env_ids);
+/* frames per slot in the last step (counts[n], may be NULL); returns the rows per slot (> 0), HSR_EINVAL when capture is off or no
+ * step ran since hsr_batch_set_capture.  Synchronises. */
+int hsr_batch_capture_counts(hsr_batch *b, int32_t *counts);
+/* host copy of the captured rows of the last step: xpos [n, rows, nlink, 3], xmat [n, rows, nlink, 9] (either may be NULL); final frame
+ * last.  Rows past a slot's count hold what the buffer held before (NaN if no step wrote them since hsr_batch_set_capture).  Synchronises. */
+int hsr_batch_capture_poses(hsr_batch *b, float *xpos, float *xmat);
+/* hsr_batch_render of the captured rows: image (slot, row) at index slot * rows + row of rgb [n, rows, H, W, 3], depth [n, rows, H, W],
+ * segid [n, rows, H, W]; the images of rows past a slot's count (other than the last) are not written.  track_body reads the frame's own
+ * poses.  Same checks as hsr_batch_render, and HSR_EINVAL when there is no captured step. */
+int hsr_batch_render_frames(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
+                            uint8_t *rgb, float *depth, int32_t *segid);
+int hsr_batch_render_frames_dev(hsr_batch *b, const float *cam, int track_body, int width, int height, const float *geom_rgba,
+                                uint8_t *d_rgb, float *d_depth, int32_t *d_segid);   /* asynchronous on hsr_batch_stream() */
 /* per-env error flags (non-finite or |q| > 1e10), the batched form of MuJoCo's mj_checkPos/Vel */
 int hsr_batch_bad_state(hsr_batch *b, uint8_t *out /*[N]*/);
 
