@@ -258,7 +258,7 @@
             const v3 t2 = cross(nrm, t1);
             const float fri[5] = {pr[1].x, pr[1].y, pr[1].z, pr[1].w, pr[2].x};
             const float solimp[5] = {pr[2].w, pr[3].x, pr[3].y, pr[3].z, pr[3].w};
-            // pair constants formed on the host (hsrsim.hip: pair_rec): B = 2 / (dmax timeconst), K = 1 / (dmax^2 timeconst^2 dampratio^2)
+            // pair constants formed on the host (host_create.h: derive_pair_rec): B = 2 / (dmax timeconst), K = 1 / (dmax^2 timeconst^2 dampratio^2)
             const float tran = pr[0].w;
             const float imp = impedance<SolimpGeneral<MT>::value>(solimp, dist);
             const float B = pr[2].y, Kimp = imp * pr[2].z;

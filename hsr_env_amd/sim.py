@@ -28,19 +28,70 @@ class MujocoException(RuntimeError):
     """Some env reached a non-finite state (reference: mujoco_py.MujocoException on MuJoCo warnings)."""
 
 
-EXPORTS = [
-    "hsr_last_error", "hsr_model_load", "hsr_model_destroy", "hsr_model_size", "hsr_model_timestep",
-    "hsr_model_ctrlrange", "hsr_model_qpos0", "hsr_model_body_id", "hsr_model_joint_qpos_addr",
-    "hsr_batch_create", "hsr_batch_destroy", "hsr_batch_size", "hsr_batch_stream", "hsr_batch_sync",
-    "hsr_batch_reset", "hsr_batch_reset_dev", "hsr_batch_get_state", "hsr_batch_set_state", "hsr_batch_set_mocap",
-    "hsr_batch_set_warmstart", "hsr_batch_get_warmstart", "hsr_batch_forward", "hsr_batch_step",
-    "hsr_batch_step_dev", "hsr_batch_body_xpos", "hsr_batch_bad_state", "hsr_batch_get_field",
-    "hsr_batch_set_profiling", "hsr_batch_last_timing", "hsr_batch_set_graph", "hsr_batch_set_persistent", "hsr_batch_is_persistent",
-    "hsr_batch_obs_openai", "hsr_batch_obs_openai_dev", "hsr_batch_set_debug", "hsr_batch_cap_counts", "hsr_batch_cap_histogram", "hsr_batch_newton_trips", "hsr_batch_packing", "hsr_batch_set_schedule", "hsr_batch_set_solo", "hsr_batch_solo_handovers", "hsr_batch_set_goals",
-    "hsr_batch_phase_cycles", "hsr_batch_block_times", "hsr_batch_kernel_times", "hsr_batch_set_queue", "hsr_batch_set_mpr_warm",
-    "hsr_model_hull_planes", "hsr_batch_render", "hsr_batch_render_dev",
-    "hsr_batch_set_capture", "hsr_batch_capture_counts", "hsr_batch_capture_poses", "hsr_batch_render_frames", "hsr_batch_render_frames_dev",
-]
+_vp, _fp_t, _u8p, _i32p = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+_ip, _ullp = C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)
+_int, _float = C.c_int, C.c_float
+_RENDER = [_vp, _fp_t, _int, _int, _int, _fp_t]          # batch, camera, track_body, width, height, geom_rgba; then rgb, depth, segid
+# the ABI as this module uses it: name -> (restype, argtypes); include/hsrsim.h declares it (tests/test_abi.py holds the two together)
+PROTOTYPES = {
+    "hsr_last_error": (C.c_char_p, []),
+    "hsr_model_load": (_int, [C.c_char_p, C.c_size_t, C.POINTER(_vp)]),
+    "hsr_model_destroy": (None, [_vp]),
+    "hsr_model_size": (_int, [_vp, _int]),
+    "hsr_model_timestep": (C.c_double, [_vp]),
+    "hsr_model_ctrlrange": (_int, [_vp, _fp_t]),
+    "hsr_model_qpos0": (_int, [_vp, _fp_t]),
+    "hsr_model_body_id": (_int, [_vp, C.c_char_p]),
+    "hsr_model_joint_qpos_addr": (_int, [_vp, C.c_char_p, _ip, _ip]),
+    "hsr_model_hull_planes": (_int, [_vp, _int, _fp_t, _int]),
+    "hsr_batch_create": (_int, [_vp, _int, _int, C.POINTER(_vp)]),
+    "hsr_batch_destroy": (None, [_vp]),
+    "hsr_batch_size": (_int, [_vp]),
+    "hsr_batch_stream": (_vp, [_vp]),
+    "hsr_batch_sync": (_int, [_vp]),
+    "hsr_batch_reset": (_int, [_vp, _u8p, _fp_t, _fp_t]),
+    "hsr_batch_reset_dev": (_int, [_vp, _vp, _vp, _vp]),
+    "hsr_batch_get_state": (_int, [_vp, _fp_t, _fp_t, _fp_t]),
+    "hsr_batch_set_state": (_int, [_vp, _fp_t, _fp_t, _fp_t]),
+    "hsr_batch_set_mocap": (_int, [_vp, _fp_t]),
+    "hsr_batch_set_warmstart": (_int, [_vp, _fp_t]),
+    "hsr_batch_get_warmstart": (_int, [_vp, _fp_t]),
+    "hsr_batch_forward": (_int, [_vp]),
+    "hsr_batch_step": (_int, [_vp, _fp_t, _int, _int, _float, _fp_t, _fp_t, _u8p, _i32p]),
+    "hsr_batch_step_dev": (_int, [_vp, _vp, _int, _int, _float, _vp, _vp, _vp, _vp]),
+    "hsr_batch_set_goals": (_int, [_vp, _int, _ip, _ip, _fp_t]),
+    "hsr_batch_body_xpos": (_int, [_vp, _int, _fp_t]),
+    "hsr_batch_obs_openai": (_int, [_vp, _ip, _fp_t]),
+    "hsr_batch_obs_openai_dev": (_int, [_vp, _ip, _vp]),
+    "hsr_batch_render": (_int, _RENDER + [_u8p, _fp_t, _i32p]),
+    "hsr_batch_render_dev": (_int, _RENDER + [_vp, _vp, _vp]),
+    "hsr_batch_set_capture": (_int, [_vp, _int, _int, _i32p]),
+    "hsr_batch_capture_counts": (_int, [_vp, _i32p]),
+    "hsr_batch_capture_poses": (_int, [_vp, _fp_t, _fp_t]),
+    "hsr_batch_render_frames": (_int, _RENDER + [_u8p, _fp_t, _i32p]),
+    "hsr_batch_render_frames_dev": (_int, _RENDER + [_vp, _vp, _vp]),
+    "hsr_batch_bad_state": (_int, [_vp, _u8p]),
+    "hsr_batch_get_field": (_int, [_vp, _int, _fp_t]),
+    "hsr_batch_set_profiling": (_int, [_vp, _int]),
+    "hsr_batch_last_timing": (_int, [_vp, _fp_t, _fp_t, _ip]),
+    "hsr_batch_kernel_times": (_int, [_vp, _fp_t, _int]),
+    "hsr_batch_set_graph": (_int, [_vp, _int]),
+    "hsr_batch_set_persistent": (_int, [_vp, _int]),
+    "hsr_batch_is_persistent": (_int, [_vp]),
+    "hsr_batch_set_debug": (_int, [_vp, _int]),
+    "hsr_batch_set_solo": (_int, [_vp, _int, _float]),
+    "hsr_batch_solo_handovers": (_int, [_vp, _ip]),
+    "hsr_batch_set_schedule": (_int, [_vp, _int]),
+    "hsr_batch_set_mpr_warm": (_int, [_vp, _int]),
+    "hsr_batch_set_queue": (_int, [_vp, _int, _int]),
+    "hsr_batch_cap_counts": (_int, [_vp, _ullp]),
+    "hsr_batch_cap_histogram": (_int, [_vp, _ullp]),
+    "hsr_batch_newton_trips": (_int, [_vp, _i32p]),
+    "hsr_batch_packing": (_int, [_vp, _i32p]),
+    "hsr_batch_phase_cycles": (_int, [_vp, _ullp]),
+    "hsr_batch_block_times": (_int, [_vp, _ullp, _int]),
+}
+EXPORTS = list(PROTOTYPES)
 
 CAPTURE_MAX = 1024          # include/hsrsim.h: HSR_CAPTURE_MAX
 
@@ -59,61 +110,9 @@ def load_library():
             f"{LIB_PATH} not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950); there is no CPU fallback for the product path.")
     L = C.CDLL(str(LIB_PATH))
-    vp, fp, u8p, i32p = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
-    L.hsr_last_error.restype = C.c_char_p
-    L.hsr_model_load.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp)]
-    L.hsr_model_destroy.argtypes = [vp]; L.hsr_model_destroy.restype = None
-    L.hsr_model_size.argtypes = [vp, C.c_int]
-    L.hsr_model_timestep.argtypes = [vp]; L.hsr_model_timestep.restype = C.c_double
-    L.hsr_model_ctrlrange.argtypes = [vp, fp]
-    L.hsr_model_qpos0.argtypes = [vp, fp]
-    L.hsr_model_body_id.argtypes = [vp, C.c_char_p]
-    L.hsr_model_joint_qpos_addr.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.hsr_batch_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
-    L.hsr_batch_destroy.argtypes = [vp]; L.hsr_batch_destroy.restype = None
-    L.hsr_batch_size.argtypes = [vp]
-    L.hsr_batch_stream.argtypes = [vp]; L.hsr_batch_stream.restype = vp
-    L.hsr_batch_sync.argtypes = [vp]
-    L.hsr_batch_reset.argtypes = [vp, u8p, fp, fp]
-    L.hsr_batch_reset_dev.argtypes = [vp, vp, vp, vp]
-    L.hsr_batch_get_state.argtypes = [vp, fp, fp, fp]
-    L.hsr_batch_set_state.argtypes = [vp, fp, fp, fp]
-    L.hsr_batch_set_mocap.argtypes = [vp, fp]
-    L.hsr_batch_set_warmstart.argtypes = [vp, fp]
-    L.hsr_batch_get_warmstart.argtypes = [vp, fp]
-    L.hsr_batch_forward.argtypes = [vp]
-    L.hsr_batch_step.argtypes = [vp, fp, C.c_int, C.c_int, C.c_float, fp, fp, u8p, i32p]
-    L.hsr_batch_step_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp, vp, vp]
-    L.hsr_batch_body_xpos.argtypes = [vp, C.c_int, fp]
-    L.hsr_batch_obs_openai.argtypes = [vp, C.POINTER(C.c_int), fp]
-    L.hsr_batch_obs_openai_dev.argtypes = [vp, C.POINTER(C.c_int), C.c_void_p]
-    L.hsr_batch_bad_state.argtypes = [vp, u8p]
-    L.hsr_batch_get_field.argtypes = [vp, C.c_int, fp]
-    L.hsr_batch_set_profiling.argtypes = [vp, C.c_int]
-    L.hsr_batch_last_timing.argtypes = [vp, fp, fp, C.POINTER(C.c_int)]
-    L.hsr_batch_kernel_times.argtypes = [vp, fp, C.c_int]
-    L.hsr_batch_set_queue.argtypes = [vp, C.c_int, C.c_int]
-    L.hsr_batch_set_mpr_warm.argtypes = [vp, C.c_int]
-    L.hsr_batch_set_graph.argtypes = [vp, C.c_int]
-    L.hsr_batch_set_persistent.argtypes = [vp, C.c_int]
-    L.hsr_batch_is_persistent.argtypes = [vp]
-    L.hsr_batch_set_debug.argtypes = [vp, C.c_int]
-    L.hsr_batch_set_schedule.argtypes = [vp, C.c_int]
-    L.hsr_batch_set_goals.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), fp]
-    L.hsr_batch_cap_counts.argtypes = [vp, C.POINTER(C.c_ulonglong)]
-    L.hsr_batch_cap_histogram.argtypes = [vp, C.POINTER(C.c_ulonglong)]
-    L.hsr_batch_newton_trips.argtypes = [vp, C.POINTER(C.c_int32)]
-    L.hsr_batch_packing.argtypes = [vp, C.POINTER(C.c_int32)]
-    L.hsr_batch_set_solo.argtypes = [vp, C.c_int, C.c_float]
-    L.hsr_batch_solo_handovers.argtypes = [vp, C.POINTER(C.c_int)]
-    L.hsr_model_hull_planes.argtypes = [vp, C.c_int, fp, C.c_int]
-    L.hsr_batch_render.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, fp, u8p, fp, i32p]
-    L.hsr_batch_render_dev.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, fp, vp, vp, vp]
-    L.hsr_batch_set_capture.argtypes = [vp, C.c_int, C.c_int, i32p]
-    L.hsr_batch_capture_counts.argtypes = [vp, i32p]
-    L.hsr_batch_capture_poses.argtypes = [vp, fp, fp]
-    L.hsr_batch_render_frames.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, fp, u8p, fp, i32p]
-    L.hsr_batch_render_frames_dev.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, fp, vp, vp, vp]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -255,37 +254,46 @@ class BatchSim:
         pal = None if geom_rgba is None else _f32(geom_rgba, (self.model.ngeom, 4))
         return cam.as_array(), int(cam.track_body), pal
 
+    def _render_host(self, fn, lead, fill, width, height, camera, rgb, depth, segmentation, geom_rgba):
+        """render / render_frames: outputs of shape lead + (H, W[, 3]); before the call they hold `fill` (rgb, depth, segmentation; None: anything)."""
+        cam, track, pal = self._render_args(camera, geom_rgba)
+        w, h = int(width), int(height)
+        ok = 1 <= w <= 4096 and 1 <= h <= 4096
+        new = lambda shape, dt, v: np.empty(shape, dt) if v is None else np.full(shape, v, dt)
+        o_rgb = new(lead + (h, w, 3), np.uint8, fill[0]) if rgb and ok else None
+        o_dep = new(lead + (h, w), np.float32, fill[1]) if depth and ok else None
+        o_seg = new(lead + (h, w), np.int32, fill[2]) if segmentation and ok else None
+        _check(self._L, fn(self._b, _fp(cam), track, w, h, _fp(pal), None if o_rgb is None else o_rgb.ctypes.data_as(C.POINTER(C.c_uint8)),
+                           _fp(o_dep), None if o_seg is None else o_seg.ctypes.data_as(C.POINTER(C.c_int32))))
+        outs = [o for o, want in ((o_rgb, rgb), (o_dep, depth), (o_seg, segmentation)) if want]
+        return outs[0] if len(outs) == 1 else tuple(outs)
+
+    def _render_dev(self, who, fn, lead, width, height, camera, rgb, depth, segmentation, geom_rgba):
+        """render_dev / render_frames_dev: check the caller's tensors (shape lead + (H, W[, 3])) and launch on the batch stream."""
+        cam, track, pal = self._render_args(camera, geom_rgba)
+        w, h = int(width), int(height)
+        for t, shape, dt in ((rgb, lead + (h, w, 3), "torch.uint8"), (depth, lead + (h, w), "torch.float32"),
+                             (segmentation, lead + (h, w), "torch.int32")):
+            if t is not None:
+                if tuple(t.shape) != shape or str(t.dtype) != dt or not t.is_contiguous() or t.device.type != "cuda":
+                    raise AssertionError(f"{who}: expected a contiguous {dt} tensor of shape {shape} on the GPU")
+                if t.device.index != self.device:
+                    raise AssertionError(f"{who}: tensor on cuda:{t.device.index}, the batch is on cuda:{self.device}")
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _check(self._L, fn(self._b, _fp(cam), track, w, h, _fp(pal), ptr(rgb), ptr(depth), ptr(segmentation)))
+
     def render(self, width, height, camera=None, rgb=True, depth=False, segmentation=False, geom_rgba=None):
         """Images of every env from one camera (include/hsrsim.h: hsr_batch_render) -> the requested ones of
         rgb uint8 [N,H,W,3], depth float32 [N,H,W] (distance along the camera axis; zfar on background), segmentation int32 [N,H,W]
         (geom id, -1 on background), in that order; a single array when one is requested.  camera: render.Camera (None: the
         model's default_camera); geom_rgba: [ngeom,4] colours (None: render.default_palette).  Poses of the last reset / forward / step."""
-        cam, track, pal = self._render_args(camera, geom_rgba)
-        w, h = int(width), int(height)
-        ok = 1 <= w <= 4096 and 1 <= h <= 4096
-        o_rgb = np.empty((self.n, h, w, 3), np.uint8) if rgb and ok else None
-        o_dep = np.empty((self.n, h, w), np.float32) if depth and ok else None
-        o_seg = np.empty((self.n, h, w), np.int32) if segmentation and ok else None
-        _check(self._L, self._L.hsr_batch_render(self._b, _fp(cam), track, w, h, _fp(pal),
-                                                 None if o_rgb is None else o_rgb.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(o_dep),
-                                                 None if o_seg is None else o_seg.ctypes.data_as(C.POINTER(C.c_int32))))
-        outs = [o for o, want in ((o_rgb, rgb), (o_dep, depth), (o_seg, segmentation)) if want]
-        return outs[0] if len(outs) == 1 else tuple(outs)
+        fn = self._L.hsr_batch_render
+        return self._render_host(fn, (self.n,), (None, None, None), width, height, camera, rgb, depth, segmentation, geom_rgba)
 
     def render_dev(self, width, height, camera=None, rgb=None, depth=None, segmentation=None, geom_rgba=None):
         """render() into caller-provided torch tensors on the batch's device (uint8 [N,H,W,3], float32 [N,H,W], int32 [N,H,W];
         None skips an output); asynchronous on the batch stream (stream_ptr)."""
-        cam, track, pal = self._render_args(camera, geom_rgba)
-        w, h = int(width), int(height)
-        for t, shape, dt in ((rgb, (self.n, h, w, 3), "torch.uint8"), (depth, (self.n, h, w), "torch.float32"),
-                             (segmentation, (self.n, h, w), "torch.int32")):
-            if t is not None:
-                if tuple(t.shape) != shape or str(t.dtype) != dt or not t.is_contiguous() or t.device.type != "cuda":
-                    raise AssertionError(f"render_dev: expected a contiguous {dt} tensor of shape {shape} on the GPU")
-                if t.device.index != self.device:
-                    raise AssertionError(f"render_dev: tensor on cuda:{t.device.index}, the batch is on cuda:{self.device}")
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _check(self._L, self._L.hsr_batch_render_dev(self._b, _fp(cam), track, w, h, _fp(pal), ptr(rgb), ptr(depth), ptr(segmentation)))
+        self._render_dev("render_dev", self._L.hsr_batch_render_dev, (self.n,), width, height, camera, rgb, depth, segmentation, geom_rgba)
 
     # -- in-step frame capture (include/hsrsim.h: hsr_batch_set_capture; the recorder of hsr/env.py:118-131)
     def set_capture(self, env_ids, every):
@@ -321,33 +329,14 @@ class BatchSim:
         """render() of the captured frames of the last step: rgb uint8 [n, rows, H, W, 3], depth float32 [n, rows, H, W], segmentation
         int32 [n, rows, H, W] (the requested ones, in that order; a single array when one is requested); row k < capture_counts()[slot]
         is frame k, the last row the final frame, the rows in between are zero (depth: NaN, segmentation: -2)."""
-        cam, track, pal = self._render_args(camera, geom_rgba)
-        w, h = int(width), int(height)
-        rows = self.capture_rows()
-        ok = 1 <= w <= 4096 and 1 <= h <= 4096
-        n = self._cap_n
-        o_rgb = np.zeros((n, rows, h, w, 3), np.uint8) if rgb and ok else None
-        o_dep = np.full((n, rows, h, w), np.nan, np.float32) if depth and ok else None
-        o_seg = np.full((n, rows, h, w), -2, np.int32) if segmentation and ok else None
-        _check(self._L, self._L.hsr_batch_render_frames(self._b, _fp(cam), track, w, h, _fp(pal),
-                                                        None if o_rgb is None else o_rgb.ctypes.data_as(C.POINTER(C.c_uint8)), _fp(o_dep),
-                                                        None if o_seg is None else o_seg.ctypes.data_as(C.POINTER(C.c_int32))))
-        outs = [o for o, want in ((o_rgb, rgb), (o_dep, depth), (o_seg, segmentation)) if want]
-        return outs[0] if len(outs) == 1 else tuple(outs)
+        fn, lead = self._L.hsr_batch_render_frames, (self._cap_n, self.capture_rows())
+        return self._render_host(fn, lead, (0, np.nan, -2), width, height, camera, rgb, depth, segmentation, geom_rgba)
 
     def render_frames_dev(self, width, height, camera=None, rgb=None, depth=None, segmentation=None, geom_rgba=None):
         """render_frames() into caller-provided torch tensors on the batch's device (uint8 [n,rows,H,W,3], float32 [n,rows,H,W], int32
         [n,rows,H,W]; None skips an output); the rows past a slot's count are left as they are.  Asynchronous on the batch stream."""
-        cam, track, pal = self._render_args(camera, geom_rgba)
-        w, h = int(width), int(height)
-        rows = self.capture_rows()
-        for t, shape, dt in ((rgb, (self._cap_n, rows, h, w, 3), "torch.uint8"), (depth, (self._cap_n, rows, h, w), "torch.float32"),
-                             (segmentation, (self._cap_n, rows, h, w), "torch.int32")):
-            if t is not None:
-                if tuple(t.shape) != shape or str(t.dtype) != dt or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != self.device:
-                    raise AssertionError(f"render_frames_dev: expected a contiguous {dt} tensor of shape {shape} on cuda:{self.device}")
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _check(self._L, self._L.hsr_batch_render_frames_dev(self._b, _fp(cam), track, w, h, _fp(pal), ptr(rgb), ptr(depth), ptr(segmentation)))
+        fn, lead = self._L.hsr_batch_render_frames_dev, (self._cap_n, self.capture_rows())
+        self._render_dev("render_frames_dev", fn, lead, width, height, camera, rgb, depth, segmentation, geom_rgba)
 
     def bad_state(self):
         out = np.empty(self.n, np.uint8)

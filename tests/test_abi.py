@@ -16,6 +16,15 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(hsr_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_batch_prototypes():
+    """(name, return type, [parameter declarations]) of every hsr_batch_* function include/hsrsim.h declares."""
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "hsrsim.h").read_text(), flags=re.S)
+    protos = [(name, ret.strip(), [p.strip() for p in params.split(",")])
+              for ret, name, params in re.findall(r"^\s*([A-Za-z_][\w \t]*?[ \t*]+)(hsr_batch_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M)]
+    assert sorted(p[0] for p in protos) == [s for s in declared_symbols() if s.startswith("hsr_batch_")]
+    return protos
+
+
 @pytest.fixture(scope="module")
 def lib():
     from hsr_env_amd.build import build_lib
@@ -28,7 +37,7 @@ def test_exports_every_declared_symbol(lib):
     for name in syms:
         assert hasattr(lib, name), f"{name} declared in include/hsrsim.h but not exported"
     from hsr_env_amd.sim import EXPORTS
-    assert set(EXPORTS) <= set(syms)
+    assert set(EXPORTS) == set(syms)          # hsr_env_amd.sim.PROTOTYPES declares the whole ABI
 
 
 def test_model_entry_points_on_cpu(lib, models):
@@ -144,3 +153,13 @@ def test_null_handles_are_refused(lib):
     assert lib.hsr_batch_body_xpos(None, 0, None) == -1
     lib.hsr_batch_destroy.argtypes = [vp]; lib.hsr_batch_destroy.restype = None
     lib.hsr_batch_destroy(None)
+    # every hsr_batch_* function the header declares, with its arity and parameter kinds taken from the declaration: NULL handle,
+    # NULL / zero for the rest -> HSR_EINVAL (hsr_batch_stream: NULL; hsr_batch_destroy: returns nothing)
+    protos = declared_batch_prototypes()
+    assert len(protos) >= 46
+    for name, ret, params in protos:
+        f = getattr(lib, name)
+        f.argtypes = [vp if "*" in p else C.c_float if p.split()[0] == "float" else C.c_int for p in params]
+        f.restype = vp if "*" in ret else None if ret == "void" else C.c_int
+        got = f(*[None if "*" in p else 0 for p in params])
+        assert got == (None if f.restype in (vp, None) else -1), name

@@ -1149,7 +1149,7 @@ def test_full_size_invariants(models, cfg, n):
 
 @pytest.mark.parametrize("cfg,n", [("cfg3", 8192), ("cfg2", 9001), ("cfg4", 300)])
 def test_packing_of_a_launch_follows_its_contract(models, cfg, n):
-    """k_schedule (hsrsim.hip): per chunk of 8192 envs the envs are ordered by the Newton iterations of their previous env-step (more first, ties:
+    """k_schedule (csrc/util_kernels.h): per chunk of 8192 envs the envs are ordered by the Newton iterations of their previous env-step (more first, ties:
     lower index first); the first lane group of task w holds the w-th of that order, the other lane groups are filled from the easy end; every env
     is held exactly once.  Checked against a numpy restatement on the iteration counts the first env-step left behind - a full chunk (every stage of
     the sorting network: in registers, across the lanes of a wave, across waves), two chunks with a ragged second one, and a 32-lane model."""

@@ -30,7 +30,7 @@ def consts(m):
     nstat = 0
     while nstat < ngeom and gl[nstat] == 0:
         nstat += 1
-    # trailing free bodies (hsrsim.hip batch_init): link l owns exactly the dofs [nv - 6 (k + 1), nv - 6 k), lin then ang
+    # trailing free bodies (host_create.h trailing_free_bodies): link l owns exactly the dofs [nv - 6 (k + 1), nv - 6 k), lin then ang
     dn, lf, da, dt, dl = a["link_dofnum"], a["link_free"], a["link_dofadr"], a["dof_type"], a["dof_link"]
     group = 16 if nv <= 16 else 32
     nfb = 0
@@ -58,7 +58,7 @@ def _f(x):
 
 
 def quat2mat(q):
-    """hsrsim.hip quat2mat_h, operation for operation (double arithmetic, then one rounding to float)"""
+    """host_create.h quat2mat_h, operation for operation (double arithmetic, then one rounding to float)"""
     import math
     n = math.sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3])
     w, x, y, z = q[0] / n, q[1] / n, q[2] / n, q[3] / n
