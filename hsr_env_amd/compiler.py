@@ -23,10 +23,14 @@ What it does (decisions H1-H7 of SURVEY.md §7 are recorded in ``Model.meta``):
 Engine semantics are restated from MuJoCo's public documentation (the engine itself is absent
 from the reference tree and from this container) - parity with mujoco-py is
 therefore unpinned; see DESIGN.md.
+
+``compile_model`` is the list of stages.  The blob container ``Model``, the table layout and the
+numpy reference the last stage uses are model.py's (what the run time imports); its names stay
+importable from here.
 """
 from __future__ import annotations
 
-import json
+import re
 import struct
 import xml.etree.ElementTree as ET
 from dataclasses import dataclass, field
@@ -35,50 +39,22 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-# MuJoCo geom type enum values (kept so tables read like mjModel)
-GEOM_PLANE, GEOM_SPHERE, GEOM_CYLINDER, GEOM_BOX, GEOM_MESH = 0, 2, 5, 6, 7
+from .model import (BLOB_MAGIC, DOF_FREE_ANG, DOF_FREE_LIN, DOF_HINGE, DOF_SLIDE,  # noqa: F401
+                    FN_BOX_BOX, FN_CONVEX, FN_MAXCON, FN_PLANE_BOX, FN_PLANE_CONVEX,
+                    GEOM_BOX, GEOM_CYLINDER, GEOM_MESH, GEOM_PLANE, GEOM_SPHERE, MODEL_DIR, UNLIMITED, _ARRAY_FIELDS,
+                    OPT_GRAV_Z, OPT_IMPRATIO, OPT_ITERATIONS, OPT_LS_ITERATIONS, OPT_LS_TOLERANCE, OPT_MEANINERTIA,
+                    OPT_MPR_ITERATIONS, OPT_MPR_TOLERANCE, OPT_TIMESTEP, OPT_TOLERANCE,
+                    SZ_NBODY, SZ_NCONMAX, SZ_NDENSE, SZ_NGEOM, SZ_NJMAX, SZ_NLIMIT, SZ_NLINK, SZ_NMESHVERT, SZ_NMOCAP,
+                    SZ_NPAIR, SZ_NQ, SZ_NSLOT, SZ_NU, SZ_NV,
+                    Model, axis_angle_quat, dof_motion, link_kinematics, load_config, mass_matrix, point_jacobian,
+                    quat_mul, quat_normalize, quat_to_mat)
+
 GEOM_TYPES = {"plane": GEOM_PLANE, "sphere": GEOM_SPHERE, "cylinder": GEOM_CYLINDER,
               "box": GEOM_BOX, "mesh": GEOM_MESH}
-# dof types
-DOF_SLIDE, DOF_HINGE, DOF_FREE_LIN, DOF_FREE_ANG = 0, 1, 2, 3
-# narrowphase function per candidate pair
-FN_PLANE_BOX, FN_PLANE_CONVEX, FN_BOX_BOX, FN_CONVEX = 0, 1, 2, 3
-UNLIMITED = 1e30     # range of an actuator without ctrllimited / forcelimited (finite in fp32)
-FN_MAXCON = {FN_PLANE_BOX: 4, FN_PLANE_CONVEX: 1, FN_BOX_BOX: 8, FN_CONVEX: 1}
 
 DEFAULT_REF_ROOT = Path("/root/reference/hsr")
 ALL_DOFS = ["slide_x", "slide_y", "arm_lift_joint", "arm_flex_joint", "wrist_roll_joint",
             "hand_l_proximal_joint", "hand_r_proximal_joint"]
-
-BLOB_MAGIC = b"HSRM0001"
-
-
-# ----------------------------------------------------------------------------- math helpers
-def quat_normalize(q):
-    q = np.asarray(q, dtype=np.float64)
-    return q / np.linalg.norm(q)
-
-
-def quat_mul(a, b):
-    aw, ax, ay, az = a
-    bw, bx, by, bz = b
-    return np.array([aw * bw - ax * bx - ay * by - az * bz,
-                     aw * bx + ax * bw + ay * bz - az * by,
-                     aw * by - ax * bz + ay * bw + az * bx,
-                     aw * bz + ax * by - ay * bx + az * bw])
-
-
-def quat_to_mat(q):
-    w, x, y, z = q
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
-
-
-def axis_angle_quat(axis, angle):
-    axis = np.asarray(axis, dtype=np.float64)
-    s = np.sin(0.5 * angle)
-    return np.array([np.cos(0.5 * angle), axis[0] * s, axis[1] * s, axis[2] * s])
 
 
 def _vec(text, n, default):
@@ -181,28 +157,30 @@ class _Body:
     inertial: Optional[dict] = None
 
 
-def _apply_setters(root, set_xml):
-    """hsr/util.py:129-135 (`for change in changes`): the path's last component is the attribute, the rest an ElementTree
-    path relative to the root of the file being mutated; a path that matches nothing in this file is skipped."""
-    import re
-    for path, value in set_xml:
-        parent = re.sub('/[^/]*$', '', str(path))
-        elt = root.find(parent)
-        if isinstance(elt, ET.Element):
-            elt.set(re.search('[^/]*$', str(path))[0], str(value))
+@dataclass
+class _Parsed:
+    """What the model needs of the mutated MJCF tree."""
+    opt: dict
+    bodies: List[_Body]
+    meshes: Dict[str, Path]
+    excludes: list
+    inertiafromgeom: bool
+    meta: dict
 
 
-def _parse_tree(ref_root: Path, xml_file: str, dofs: Sequence[str], n_blocks: int,
-                block_pos: np.ndarray, set_xml=(), block_geom=None):
-    xml_path = ref_root / xml_file
-    root = ET.parse(xml_path).getroot()
-    meta = {}
-    # -- block injection (util.py:106-127), then the --set-xml changes (util.py:129-135), file by file as mutate_tree does
-    worldbody = root.find("worldbody")
-    for i in range(n_blocks):
+# ----------------------------------------------------------------------------- the reference's XML mutations
+def _block_positions(block_pos, n_blocks: int) -> np.ndarray:
+    if block_pos is None:
+        # resting height on the pan: 0.405 + 0.017 (world.xml:83-84, util.py:120)
+        block_pos = [[0.0, 0.12 * (i - (n_blocks - 1) / 2.0), 0.422] for i in range(n_blocks)]
+    return np.asarray(block_pos, dtype=np.float64).reshape(n_blocks, 3)
+
+
+def _inject_blocks(worldbody, block_pos, block_geom=None):
+    """hsr/util.py:106-127: one free body `block<i>` with one geom per row of block_pos."""
+    for i, pos in enumerate(block_pos):
         name = f"block{i}"
-        body = ET.SubElement(worldbody, "body",
-                             attrib=dict(name=name, pos=" ".join(repr(float(x)) for x in block_pos[i])))
+        body = ET.SubElement(worldbody, "body", attrib=dict(name=name, pos=" ".join(repr(float(x)) for x in pos)))
         gattr = dict(name=name, type="box", mass="1", size=".05 .025 .017", condim="6", solimp="0.99 0.99 0.01", solref="0.01 1")
         if block_geom:              # test scenes only: another shape for the injected body (e.g. one of the robot's hulls as a free body)
             gattr.update(block_geom)
@@ -210,37 +188,41 @@ def _parse_tree(ref_root: Path, xml_file: str, dofs: Sequence[str], n_blocks: in
                 gattr.pop("size", None)
         ET.SubElement(body, "geom", attrib=gattr)
         ET.SubElement(body, "freejoint", attrib=dict(name=f"block{i}joint"))
+
+
+def _apply_setters(root, set_xml):
+    """hsr/util.py:129-135 (`for change in changes`): the path's last component is the attribute, the rest an ElementTree
+    path relative to the root of the file being mutated; a path that matches nothing in this file is skipped."""
+    for path, value in set_xml:
+        parent = re.sub('/[^/]*$', '', str(path))
+        elt = root.find(parent)
+        if isinstance(elt, ET.Element):
+            elt.set(re.search('[^/]*$', str(path))[0], str(value))
+
+
+def _filter_dofs(root, dofs) -> list:
+    """hsr/util.py:137-146 (`--use-dof`): removes the actuators and joints of every other dof -> the actuators that stay."""
+    kept = []
+    for acts in root.iter("actuator"):
+        for a in list(acts):
+            if a.get("joint") in dofs:
+                kept.append(a)
+            else:
+                acts.remove(a)
+    for body in root.iter("body"):
+        for j in body.findall("joint"):
+            if j.get("name") not in dofs:
+                body.remove(j)
+    return kept
+
+
+def _mutated_tree(xml_path: Path, dofs, block_pos, set_xml, block_geom):
+    """The tree mujoco-py would have loaded -> (root, actuator elements): block injection, then the --set-xml changes, file by
+    file as mutate_tree does, with the included files spliced in (util.py:148-151 keeps includes relative), then the dof filter."""
+    root = ET.parse(xml_path).getroot()
+    worldbody = root.find("worldbody")
+    _inject_blocks(worldbody, block_pos, block_geom)
     _apply_setters(root, set_xml)
-
-    # -- options / compiler -------------------------------------------------------------
-    opt = {"timestep": 0.002, "impratio": 1.0, "cone": "pyramidal"}
-    for o in root.findall("option"):
-        for k in ("timestep", "impratio"):
-            if o.get(k) is not None:
-                opt[k] = float(o.get(k))
-        if o.get("cone") is not None:
-            opt["cone"] = o.get("cone")
-    comp = root.find("compiler")
-    degree = comp.get("angle", "degree") == "degree"
-    inertiafromgeom = comp.get("inertiafromgeom", "auto") == "true"
-    meshdir = (xml_path.parent / comp.get("meshdir", ".")).resolve()
-    size = root.find("size")
-    opt["njmax"] = int(size.get("njmax", 500))
-    opt["nconmax"] = int(size.get("nconmax", 100))
-
-    # -- defaults (H3) --------------------------------------------------------------------
-    geom_global: Dict[str, str] = {}
-    geom_class: Dict[str, Dict[str, str]] = {}
-    for top in root.findall("default"):
-        for g in top.findall("geom"):
-            geom_global.update(g.attrib)
-        for sub in top.findall("default"):
-            for g in sub.findall("geom"):
-                geom_class.setdefault(sub.get("class"), {}).update(g.attrib)
-
-    meshes = {m.get("name"): meshdir / m.get("file") for m in root.find("asset").findall("mesh")}
-
-    # -- splice <include> (util.py:148-151 keeps includes relative) -----------------------
     for i, child in enumerate(list(worldbody)):
         if child.tag == "include":
             inc = ET.parse(xml_path.parent / child.get("file")).getroot()
@@ -248,29 +230,38 @@ def _parse_tree(ref_root: Path, xml_file: str, dofs: Sequence[str], n_blocks: in
             worldbody.remove(child)
             for j, b in enumerate(list(inc)):
                 worldbody.insert(i + j, b)
+    return root, _filter_dofs(root, dofs)
 
-    # -- DOF filter (util.py:137-146) ---------------------------------------------------------
-    actuators = []
-    for acts in root.iter("actuator"):
-        for a in list(acts):
-            if a.get("joint") in dofs:
-                actuators.append(a)
-    for body in root.iter("body"):
-        for j in body.findall("joint"):
-            if j.get("name") not in dofs:
-                body.remove(j)
 
-    excludes = [(e.get("body1"), e.get("body2")) for c in root.findall("contact")
-                for e in c.findall("exclude")]
+# ----------------------------------------------------------------------------- reading the tree
+def _read_options(root) -> dict:
+    opt = {"timestep": 0.002, "impratio": 1.0, "cone": "pyramidal"}
+    for o in root.findall("option"):
+        for k in ("timestep", "impratio"):
+            if o.get(k) is not None:
+                opt[k] = float(o.get(k))
+        if o.get("cone") is not None:
+            opt["cone"] = o.get("cone")
+    size = root.find("size")
+    opt["njmax"] = int(size.get("njmax", 500))
+    opt["nconmax"] = int(size.get("nconmax", 100))
+    return opt
 
-    # -- walk bodies -------------------------------------------------------------------------
-    bodies: List[_Body] = [_Body("world", np.zeros(3), np.array([1., 0, 0, 0]), False, -1)]
 
-    def parse_geom(g, idx):
-        at = dict(geom_global)
-        at.update(geom_class.get(g.get("class"), {}))
+@dataclass
+class _BodyReader:
+    """Walks the body tree depth first into `bodies`; geom attributes resolve global default < class default < own (H3)."""
+    degree: bool
+    geom_global: Dict[str, str]
+    geom_class: Dict[str, Dict[str, str]]
+    bodies: List[_Body]
+    meta: dict
+    ngeom: int = 0
+
+    def geom(self, g) -> _Geom:
+        at = dict(self.geom_global)
+        at.update(self.geom_class.get(g.get("class"), {}))
         at.update(g.attrib)
-        gtype = GEOM_TYPES[at.get("type", "sphere")]
         solimp = np.array([0.9, 0.95, 0.001, 0.5, 2.0])
         if "solimp" in at:
             v = [float(t) for t in at["solimp"].split()]
@@ -279,7 +270,8 @@ def _parse_tree(ref_root: Path, xml_file: str, dofs: Sequence[str], n_blocks: in
         if "friction" in at:
             v = [float(t) for t in at["friction"].split()]
             fr[:len(v)] = v
-        return _Geom(name=at.get("name", f"geom{idx}"), type=gtype,
+        self.ngeom += 1
+        return _Geom(name=at.get("name", f"geom{self.ngeom - 1}"), type=GEOM_TYPES[at.get("type", "sphere")],
                      size=_vec(at.get("size"), 3, [0, 0, 0]),
                      pos=_vec(at.get("pos"), 3, [0, 0, 0]),
                      quat=quat_normalize(_vec(at.get("quat"), 4, [1, 0, 0, 0])),
@@ -289,285 +281,530 @@ def _parse_tree(ref_root: Path, xml_file: str, dofs: Sequence[str], n_blocks: in
                      mass=float(at["mass"]) if "mass" in at else None,
                      density=float(at.get("density", 1000.0)))
 
-    ngeom_seen = [0]
+    def joint(self, j) -> _Joint:
+        if j.tag == "freejoint":
+            return _Joint(name=j.get("name"), type="free", axis=np.zeros(3), pos=np.zeros(3), limited=False,
+                          range=np.zeros(2), damping=0.0)
+        jt = j.get("type", "hinge")
+        rng = _vec(j.get("range"), 2, [0, 0])
+        if jt == "hinge" and self.degree:
+            rng = np.deg2rad(rng)
+        return _Joint(name=j.get("name"), type=jt,
+                      axis=quat_normalize(_vec(j.get("axis"), 3, [0, 0, 1])),
+                      pos=_vec(j.get("pos"), 3, [0, 0, 0]),
+                      limited=j.get("limited", "false") == "true", range=rng,
+                      damping=float(j.get("damping", 0.0)))
 
-    def walk(elem, parent_id):
-        for g in elem.findall("geom"):
-            bodies[parent_id].geoms.append(parse_geom(g, ngeom_seen[0]))
-            ngeom_seen[0] += 1
+    def body(self, b, parent_id: int) -> _Body:
+        body = _Body(name=b.get("name"), pos=_vec(b.get("pos"), 3, [0, 0, 0]),
+                     quat=quat_normalize(_vec(b.get("quat"), 4, [1, 0, 0, 0])),
+                     mocap=b.get("mocap", "false") == "true", parent=parent_id)
+        if b.get("pos") is not None and _vec(b.get("pos"), 3, [np.nan] * 3)[0] != body.pos[0]:
+            self.meta.setdefault("H1_malformed_pos", []).append(b.get("name"))
+        body.joints = [self.joint(j) for j in b.findall("joint")] + [self.joint(j) for j in b.findall("freejoint")]
+        inert = b.find("inertial")
+        if inert is not None:
+            body.inertial = dict(pos=_vec(inert.get("pos"), 3, [0, 0, 0]),
+                                 quat=quat_normalize(_vec(inert.get("quat"), 4, [1, 0, 0, 0])),
+                                 mass=float(inert.get("mass")),
+                                 diag=_vec(inert.get("diaginertia"), 3, [0, 0, 0]))
+        return body
+
+    def walk(self, elem, parent_id: int):
+        self.bodies[parent_id].geoms += [self.geom(g) for g in elem.findall("geom")]
         for b in elem.findall("body"):
-            body = _Body(name=b.get("name"), pos=_vec(b.get("pos"), 3, [0, 0, 0]),
-                         quat=quat_normalize(_vec(b.get("quat"), 4, [1, 0, 0, 0])),
-                         mocap=b.get("mocap", "false") == "true", parent=parent_id)
-            if b.get("pos") is not None and _vec(b.get("pos"), 3, [np.nan] * 3)[0] != body.pos[0]:
-                meta.setdefault("H1_malformed_pos", []).append(b.get("name"))
-            for j in b.findall("joint"):
-                jt = j.get("type", "hinge")
-                rng = _vec(j.get("range"), 2, [0, 0])
-                if jt == "hinge" and degree:
-                    rng = np.deg2rad(rng)
-                bodies_j = _Joint(name=j.get("name"), type=jt,
-                                  axis=quat_normalize(_vec(j.get("axis"), 3, [0, 0, 1])),
-                                  pos=_vec(j.get("pos"), 3, [0, 0, 0]),
-                                  limited=j.get("limited", "false") == "true", range=rng,
-                                  damping=float(j.get("damping", 0.0)))
-                body.joints.append(bodies_j)
-            for j in b.findall("freejoint"):
-                body.joints.append(_Joint(name=j.get("name"), type="free", axis=np.zeros(3),
-                                          pos=np.zeros(3), limited=False, range=np.zeros(2),
-                                          damping=0.0))
-            inert = b.find("inertial")
-            if inert is not None:
-                body.inertial = dict(pos=_vec(inert.get("pos"), 3, [0, 0, 0]),
-                                     quat=quat_normalize(_vec(inert.get("quat"), 4, [1, 0, 0, 0])),
-                                     mass=float(inert.get("mass")),
-                                     diag=_vec(inert.get("diaginertia"), 3, [0, 0, 0]))
-            bodies.append(body)
-            walk(b, len(bodies) - 1)
-
-    walk(worldbody, 0)
-    return dict(opt=opt, bodies=bodies, meshes=meshes, actuators=actuators, excludes=excludes,
-                inertiafromgeom=inertiafromgeom, meta=meta)
+            self.bodies.append(self.body(b, parent_id))
+            self.walk(b, len(self.bodies) - 1)
 
 
-# ----------------------------------------------------------------------------- the model
-_ARRAY_FIELDS = [
-    # scalars packed as arrays for a uniform container
-    "sizes", "opt",
-    "qpos0",
-    "link_parent", "link_pos", "link_quat", "link_dofadr", "link_dofnum", "link_qposadr",
-    "link_free", "link_mass", "link_com", "link_inertia", "link_dofmask",
-    "dof_link", "dof_type", "dof_axis", "dof_pos", "dof_parent", "dof_damping", "dof_qposadr",
-    "dof_invweight0", "dof_limited", "dof_range", "dof_solref", "dof_solimp",
-    "body_link", "body_pos", "body_quat", "body_mocap",
-    "geom_type", "geom_link", "geom_body", "geom_pos", "geom_quat", "geom_size", "geom_rbound",
-    "geom_condim", "geom_meshadr", "geom_meshnum", "geom_invweight", "geom_aabb",
-    "mesh_vert",
-    "pair_geom1", "pair_geom2", "pair_fn", "pair_condim", "pair_slot", "pair_friction",
-    "pair_solref", "pair_solimp",
-    "act_dof", "act_gear", "act_kp", "act_ctrlrange", "act_forcerange",
-]
+def _read_tree(root, xml_path: Path) -> _Parsed:
+    comp = root.find("compiler")
+    meshdir = (xml_path.parent / comp.get("meshdir", ".")).resolve()
+    reader = _BodyReader(degree=comp.get("angle", "degree") == "degree", geom_global={}, geom_class={}, meta={},
+                         bodies=[_Body("world", np.zeros(3), np.array([1., 0, 0, 0]), False, -1)])
+    for top in root.findall("default"):
+        for g in top.findall("geom"):
+            reader.geom_global.update(g.attrib)
+        for sub in top.findall("default"):
+            for g in sub.findall("geom"):
+                reader.geom_class.setdefault(sub.get("class"), {}).update(g.attrib)
+    reader.walk(root.find("worldbody"), 0)
+    return _Parsed(opt=_read_options(root), bodies=reader.bodies, meta=reader.meta,
+                   meshes={m.get("name"): meshdir / m.get("file") for m in root.find("asset").findall("mesh")},
+                   excludes=[(e.get("body1"), e.get("body2")) for c in root.findall("contact") for e in c.findall("exclude")],
+                   inertiafromgeom=comp.get("inertiafromgeom", "auto") == "true")
 
-# index constants into ``sizes`` / ``opt`` (mirrored in include/hsrsim.h and oracle/hsr_oracle.c)
-SZ_NQ, SZ_NV, SZ_NU, SZ_NLINK, SZ_NBODY, SZ_NGEOM, SZ_NPAIR, SZ_NMESHVERT, SZ_NSLOT, \
-    SZ_NLIMIT, SZ_NCONMAX, SZ_NJMAX, SZ_NMOCAP, SZ_NDENSE = range(14)
-OPT_TIMESTEP, OPT_IMPRATIO, OPT_GRAV_Z, OPT_TOLERANCE, OPT_ITERATIONS, OPT_LS_ITERATIONS, \
-    OPT_LS_TOLERANCE, OPT_MPR_TOLERANCE, OPT_MPR_ITERATIONS, OPT_MEANINERTIA = range(10)
+
+# ----------------------------------------------------------------------------- compile: records of the stages
+@dataclass
+class _Mesh:
+    volume: float
+    com: np.ndarray
+    inertia: np.ndarray      # about com, unit density
+    hull: np.ndarray
+
+
+class _MeshCache:
+    """Mass properties (MuJoCo's legacy rule) and convex hull per mesh name; every STL file is read once."""
+
+    def __init__(self, files: Dict[str, Path]):
+        self.files, self.data = files, {}
+
+    def __getitem__(self, name: str) -> _Mesh:
+        if name not in self.data:
+            tris = load_stl(self.files[name])
+            self.data[name] = _Mesh(*mesh_inertia_legacy(tris), convex_hull_vertices(tris.reshape(-1, 3)))
+        return self.data[name]
 
 
 @dataclass
-class Model:
-    arrays: Dict[str, np.ndarray]
-    names: Dict[str, List[str]]
-    meta: Dict[str, object]
-
-    def __getattr__(self, k):
-        arrays = object.__getattribute__(self, "arrays")
-        if k in arrays:
-            return arrays[k]
-        raise AttributeError(k)
-
-    # -- sizes
-    @property
-    def nq(self): return int(self.arrays["sizes"][SZ_NQ])
-    @property
-    def nv(self): return int(self.arrays["sizes"][SZ_NV])
-    @property
-    def nu(self): return int(self.arrays["sizes"][SZ_NU])
-    @property
-    def nlink(self): return int(self.arrays["sizes"][SZ_NLINK])
-    @property
-    def nbody(self): return int(self.arrays["sizes"][SZ_NBODY])
-    @property
-    def ngeom(self): return int(self.arrays["sizes"][SZ_NGEOM])
-    @property
-    def npair(self): return int(self.arrays["sizes"][SZ_NPAIR])
-    @property
-    def nslot(self): return int(self.arrays["sizes"][SZ_NSLOT])
-    @property
-    def timestep(self): return float(self.arrays["opt"][OPT_TIMESTEP])
-
-    def body_id(self, name: str) -> int:
-        return self.names["body"].index(name)
-
-    def scalar_joints(self):
-        """(qpos addresses, dof addresses) of the 1-dof joints (the robot), in joint order; scenes differ in whether the
-        block's free joint comes before (cupboard-world.xml) or after (world.xml + util.py injection) the robot."""
-        qa = [a for (a, n) in self.meta["joint_qposadr"] if n == 1]
-        da = [d for (a, n), d in zip(self.meta["joint_qposadr"], self.meta["joint_dofadr"]) if n == 1]
-        return np.array(qa, dtype=int), np.array(da, dtype=int)
-
-    def free_joint_qadrs(self):
-        """qpos start address of every free joint (x y z qw qx qy qz), in joint order."""
-        return [a for (a, n) in self.meta["joint_qposadr"] if n == 7]
-
-    def block_body(self) -> str:
-        """Name of the first free body: `block0` (util.py:109) or `block` (cupboard-world.xml:113)."""
-        for cand in ("block0", "block"):
-            if cand in self.names["body"]:
-                return cand
-        return ""
-
-    def joint_qpos_addr(self, name: str):
-        """mujoco_py ``model.get_joint_qpos_addr`` (reference use: hsr/env.py:153)."""
-        j = self.names["joint"].index(name)
-        adr, n = self.meta["joint_qposadr"][j]
-        return adr if n == 1 else (adr, adr + n)
-
-    # -- (de)serialisation ------------------------------------------------------------------
-    def to_bytes(self) -> bytes:
-        """Container: magic | u32 n | n x (name[32], u32 dtype, u32 ndim, u32 shape[4], u64 off,
-        u64 nbytes) | json_len u64 | json | data (8-byte aligned).  dtype 0=f64, 1=i32."""
-        entries, blobs, off = [], [], 0
-        for name in _ARRAY_FIELDS:
-            a = self.arrays[name]
-            if a.dtype.kind == "f":
-                a = np.ascontiguousarray(a, dtype="<f8"); code = 0
-            else:
-                a = np.ascontiguousarray(a, dtype="<i4"); code = 1
-            shape = list(a.shape) + [0] * (4 - a.ndim)
-            raw = a.tobytes()
-            pad = (-len(raw)) % 8
-            entries.append(struct.pack("<32sII4IQQ", name.encode(), code, a.ndim, *shape, off, len(raw)))
-            blobs.append(raw + b"\0" * pad)
-            off += len(raw) + pad
-        js = json.dumps(dict(names=self.names, meta=self.meta)).encode()
-        js += b" " * ((-len(js)) % 8)
-        head = BLOB_MAGIC + struct.pack("<I", len(entries)) + b"\0" * 4
-        return head + b"".join(entries) + struct.pack("<Q", len(js)) + js + b"".join(blobs)
-
-    @staticmethod
-    def from_bytes(raw: bytes) -> "Model":
-        assert raw[:8] == BLOB_MAGIC, "not an HSRM blob"
-        n = struct.unpack("<I", raw[8:12])[0]
-        p = 16
-        ents = []
-        esz = struct.calcsize("<32sII4IQQ")
-        for _ in range(n):
-            ents.append(struct.unpack("<32sII4IQQ", raw[p:p + esz])); p += esz
-        jl = struct.unpack("<Q", raw[p:p + 8])[0]; p += 8
-        js = json.loads(raw[p:p + jl].decode()); p += jl
-        arrays = {}
-        for name, code, ndim, s0, s1, s2, s3, off, nb in ents:
-            shape = (s0, s1, s2, s3)[:ndim]
-            dt = "<f8" if code == 0 else "<i4"
-            arrays[name.rstrip(b"\0").decode()] = np.frombuffer(
-                raw, dtype=dt, count=nb // (8 if code == 0 else 4), offset=p + off).reshape(shape).copy()
-        return Model(arrays=arrays, names=js["names"], meta=js["meta"])
-
-    def save(self, path):
-        Path(path).write_bytes(self.to_bytes())
-
-    @staticmethod
-    def load(path) -> "Model":
-        return Model.from_bytes(Path(path).read_bytes())
+class _Shape:
+    """A geom's shape in its own frame, unit density."""
+    volume: float
+    inertia: np.ndarray      # about the centre
+    rbound: float
+    size: np.ndarray
+    aabb: np.ndarray         # box containing the geom: centre(3) + half extents(3); tight (asymmetric) for hulls
+    com: np.ndarray = field(default_factory=lambda: np.zeros(3))     # the centre: the frame origin except for a mesh
+    verts: Optional[np.ndarray] = None                               # mesh: hull vertices about the centre
 
 
-# ----------------------------------------------------------------------------- numpy reference
-def link_kinematics(m: Model, qpos: np.ndarray):
-    """fp64 forward kinematics over links -> (xpos[nlink,3], xquat[nlink,4]).
+@dataclass
+class _MassProps:
+    mass: float = 0.0
+    com: np.ndarray = field(default_factory=lambda: np.zeros(3))
+    inertia: np.ndarray = field(default_factory=lambda: np.zeros((3, 3)))      # about com
 
-    Restates mj_kinematics for the folded tree: body frame = parent * (pos, quat); joints of a
-    body applied in order (slide: translate along the current axis; hinge: rotate about the
-    anchor); free joint: pose read from qpos with the quaternion normalised.
-    """
-    nl = m.nlink
-    xpos = np.zeros((nl, 3)); xquat = np.zeros((nl, 4)); xquat[0, 0] = 1
-    for l in range(1, nl):
-        if m.link_free[l]:
-            a = m.link_qposadr[l]
-            xpos[l] = qpos[a:a + 3]
-            xquat[l] = quat_normalize(qpos[a + 3:a + 7])
+
+@dataclass
+class _Link:
+    body: int                # the jointed body that heads the link
+    parent: int
+    pos: np.ndarray          # in the parent link's frame
+    quat: np.ndarray
+    inertial: _MassProps = field(default_factory=_MassProps)         # in the link frame
+    dofadr: int = 0          # the next four: written by assign_dofs
+    dofnum: int = 0
+    qposadr: int = 0
+    free: int = 0
+
+
+@dataclass
+class _Fold:
+    links: List[_Link]
+    body_link: np.ndarray
+    body_pos: np.ndarray     # pose of every joint-less body in its link's frame (identity for the body that heads a link)
+    body_quat: np.ndarray
+
+
+@dataclass
+class _Dof:
+    link: int
+    type: int
+    axis: np.ndarray
+    pos: np.ndarray
+    parent: int
+    damping: float
+    qposadr: int
+    limited: int
+    range: np.ndarray
+
+
+@dataclass
+class _JointAddr:
+    name: str
+    qposadr: int
+    nq: int                  # 7: free joint, 1: slide / hinge
+    dofadr: int
+
+
+@dataclass
+class _CollGeom:
+    name: str
+    geom: _Geom              # contype / conaffinity / condim / friction / solref / solimp as parsed
+    link: int
+    body: int
+    pos: np.ndarray          # in the link frame
+    quat: np.ndarray
+    shape: _Shape
+    meshadr: int
+    meshnum: int
+
+
+@dataclass
+class _Pair:
+    g1: int
+    g2: int
+    fn: int
+    condim: int
+    friction: np.ndarray
+    solref: np.ndarray
+    solimp: np.ndarray
+
+
+# ----------------------------------------------------------------------------- compile: the stages
+def geom_shape(g: _Geom, meshes: _MeshCache) -> _Shape:
+    """The one place that knows the geom types."""
+    s = g.size
+    if g.type == GEOM_PLANE:
+        return _Shape(0.0, np.zeros((3, 3)), 0.0, s, np.zeros(6))
+    if g.type == GEOM_BOX:
+        a, b, c = s
+        vol = 8 * a * b * c
+        return _Shape(vol, vol / 3.0 * np.diag([b * b + c * c, a * a + c * c, a * a + b * b]), np.linalg.norm(s), s,
+                      np.concatenate([np.zeros(3), s]))
+    if g.type == GEOM_SPHERE:
+        r = s[0]
+        vol = 4.0 / 3.0 * np.pi * r ** 3
+        return _Shape(vol, 0.4 * vol * r * r * np.eye(3), r, s, np.array([0, 0, 0, r, r, r]))
+    if g.type == GEOM_CYLINDER:
+        r, hh = s[0], s[1]
+        vol = np.pi * r * r * 2 * hh
+        ixx = vol * (3 * r * r + 4 * hh * hh) / 12.0
+        return _Shape(vol, np.diag([ixx, ixx, 0.5 * vol * r * r]), np.hypot(r, hh), s, np.array([0, 0, 0, r, r, hh]))
+    if g.type == GEOM_MESH:
+        md = meshes[g.mesh]
+        verts = md.hull - md.com
+        lo, hi = verts.min(0), verts.max(0)
+        return _Shape(md.volume, md.inertia, np.linalg.norm(verts, axis=1).max(), np.abs(verts).max(0),
+                      np.concatenate([(lo + hi) / 2, (hi - lo) / 2]), com=md.com, verts=verts)
+    raise ValueError(g.type)
+
+
+def _geom_mass_props(g: _Geom, meshes: _MeshCache):
+    """-> (mass, com in body frame, inertia about com in body frame)"""
+    sh = geom_shape(g, meshes)
+    if g.type == GEOM_PLANE:
+        return 0.0, np.zeros(3), np.zeros((3, 3))
+    Rg = quat_to_mat(g.quat)
+    mass = g.mass if g.mass is not None else g.density * sh.volume
+    scale = mass / sh.volume
+    return mass, g.pos + Rg @ sh.com, Rg @ (sh.inertia * scale) @ Rg.T
+
+
+def _combine(parts) -> _MassProps:
+    """Rigidly joined (mass, com, inertia about com) parts in one frame; the sums run in the order given."""
+    mtot = sum(p[0] for p in parts)
+    com = sum(p[0] * p[1] for p in parts) / mtot
+    I = np.zeros((3, 3))
+    for mm, c, Ic in parts:
+        d = c - com
+        I += Ic + mm * (d @ d * np.eye(3) - np.outer(d, d))
+    return _MassProps(mtot, com, I)
+
+
+def body_inertias(bodies: List[_Body], inertiafromgeom: bool, meshes: _MeshCache) -> List[_MassProps]:
+    """Mass properties of every body in its own frame: from its geoms (H2), else from its <inertial>."""
+    out = [_MassProps()]
+    for b in bodies[1:]:
+        parts = [_geom_mass_props(g, meshes) for g in b.geoms] if inertiafromgeom else []
+        parts = [p for p in parts if p[0] > 0]
+        if parts:
+            out.append(_combine(parts))
+        elif b.inertial is not None:
+            Ri = quat_to_mat(b.inertial["quat"])
+            out.append(_MassProps(b.inertial["mass"], b.inertial["pos"], Ri @ np.diag(b.inertial["diag"]) @ Ri.T))
+        else:
+            out.append(_MassProps())
+    return out
+
+
+def fold_links(bodies: List[_Body], inertials: List[_MassProps]) -> _Fold:
+    """Every joint-less body becomes part of its nearest jointed ancestor's link (link 0: the world)."""
+    nb = len(bodies)
+    body_link = np.zeros(nb, dtype=np.int32)
+    body_pos = np.zeros((nb, 3)); body_quat = np.tile([1., 0, 0, 0], (nb, 1))
+    links = [_Link(body=0, parent=0, pos=np.zeros(3), quat=np.array([1., 0, 0, 0]))]
+    for i in range(1, nb):
+        b = bodies[i]
+        p = b.parent
+        # pose of this body in its parent's link frame
+        Rp = quat_to_mat(body_quat[p])
+        pos_in_l = body_pos[p] + Rp @ b.pos
+        quat_in_l = quat_normalize(quat_mul(body_quat[p], b.quat))
+        if b.joints:
+            links.append(_Link(body=i, parent=int(body_link[p]), pos=pos_in_l, quat=quat_in_l))
+            body_link[i] = len(links) - 1
+        else:
+            body_link[i] = body_link[p]
+            body_pos[i], body_quat[i] = pos_in_l, quat_in_l
+    for l in range(1, len(links)):
+        parts = []
+        for i in range(nb):
+            if body_link[i] == l and inertials[i].mass > 0:
+                Rb = quat_to_mat(body_quat[i])
+                parts.append((inertials[i].mass, body_pos[i] + Rb @ inertials[i].com, Rb @ inertials[i].inertia @ Rb.T))
+        links[l].inertial = _combine(parts)
+    return _Fold(links, body_link, body_pos, body_quat)
+
+
+def assign_dofs(bodies: List[_Body], links: List[_Link]):
+    """-> (dofs, qpos0, joint addresses), joints in link order; writes each link's dofadr / dofnum / qposadr / free."""
+    dofs: List[_Dof] = []
+    qpos0: list = []
+    joints: List[_JointAddr] = []
+    last_dof_of_link = {0: -1}
+    for l, lk in enumerate(links):
+        if l == 0:
             continue
-        p = m.link_parent[l]
-        R = quat_to_mat(xquat[p])
-        pos = xpos[p] + R @ m.link_pos[l]
-        quat = quat_mul(xquat[p], m.link_quat[l])
-        for d in range(m.link_dofadr[l], m.link_dofadr[l] + m.link_dofnum[l]):
-            q = qpos[m.dof_qposadr[d]]
-            Rl = quat_to_mat(quat)
-            if m.dof_type[d] == DOF_SLIDE:
-                pos = pos + Rl @ m.dof_axis[d] * q
+        b = bodies[lk.body]
+        lk.dofadr, lk.qposadr = len(dofs), len(qpos0)
+        prev = last_dof_of_link[lk.parent]
+        for j in b.joints:
+            if j.type == "free":
+                assert len(b.joints) == 1 and lk.parent == 0
+                lk.free = 1
+                joints.append(_JointAddr(j.name, len(qpos0), 7, len(dofs)))
+                qa = len(qpos0)
+                qpos0 += list(lk.pos) + list(lk.quat)
+                for k in range(6):
+                    # translational dofs address qpos[qa+k]; rotational ones the quaternion start
+                    dofs.append(_Dof(link=l, type=DOF_FREE_LIN if k < 3 else DOF_FREE_ANG, axis=np.eye(3)[k % 3], pos=np.zeros(3),
+                                     parent=prev, damping=0.0, qposadr=qa + k if k < 3 else qa + 3, limited=0, range=np.zeros(2)))
+                    prev = len(dofs) - 1
             else:
-                anchor = pos + Rl @ m.dof_pos[d]
-                quat = quat_mul(quat, axis_angle_quat(m.dof_axis[d], q))
-                pos = anchor - quat_to_mat(quat) @ m.dof_pos[d]
-        xpos[l], xquat[l] = pos, quat_normalize(quat)
-    return xpos, xquat
+                joints.append(_JointAddr(j.name, len(qpos0), 1, len(dofs)))
+                dofs.append(_Dof(link=l, type=DOF_SLIDE if j.type == "slide" else DOF_HINGE, axis=j.axis, pos=j.pos, parent=prev,
+                                 damping=j.damping, qposadr=len(qpos0), limited=int(j.limited), range=j.range))
+                prev = len(dofs) - 1
+                qpos0.append(0.0)
+        lk.dofnum = len(dofs) - lk.dofadr
+        last_dof_of_link[l] = prev
+        # a non-free link may hold several slides or exactly one hinge (keeps dof axes = final frame)
+        types = [d.type for d in dofs[lk.dofadr:]]
+        assert lk.free or types.count(DOF_HINGE) == 0 or len(types) == 1, "mixed joints on a body"
+    return dofs, qpos0, joints
 
 
-def dof_motion(m: Model, xpos, xquat, qpos):
-    """World-frame motion axes: for each dof (ang[3], lin-axis[3], anchor[3])."""
-    nv = m.nv
-    ang = np.zeros((nv, 3)); lin = np.zeros((nv, 3)); anchor = np.zeros((nv, 3))
-    for l in range(1, m.nlink):
-        R = quat_to_mat(xquat[l])
-        if m.link_free[l]:
-            d0 = m.link_dofadr[l]
-            for k in range(3):
-                lin[d0 + k, k] = 1.0
-                ang[d0 + 3 + k] = R[:, k]
-                anchor[d0 + 3 + k] = xpos[l]
+def collidable_geoms(bodies: List[_Body], fold: _Fold, meshes: _MeshCache):
+    """-> (geoms with a contype or conaffinity bit, placed in their link's frame; hull vertices of the mesh geoms, concatenated)"""
+    geoms: List[_CollGeom] = []
+    mesh_vert = []
+    for i, b in enumerate(bodies):
+        for g in b.geoms:
+            if g.contype == 0 and g.conaffinity == 0:
+                continue
+            Rb = quat_to_mat(fold.body_quat[i])
+            pos = fold.body_pos[i] + Rb @ g.pos
+            quat = quat_normalize(quat_mul(fold.body_quat[i], g.quat))
+            sh = geom_shape(g, meshes)
+            meshadr, meshnum = 0, 0
+            if sh.verts is not None:
+                # geom frame origin := mesh centre of mass (MuJoCo recentres meshes)
+                pos = pos + quat_to_mat(quat) @ sh.com
+                meshadr, meshnum = sum(len(v) for v in mesh_vert), len(sh.verts)
+                mesh_vert.append(sh.verts)
+            geoms.append(_CollGeom(name=g.name if g.mesh is None else f"{b.name}:{g.mesh}", geom=g, link=int(fold.body_link[i]),
+                                   body=i, pos=pos, quat=quat, shape=sh, meshadr=meshadr, meshnum=meshnum))
+    return geoms, (np.concatenate(mesh_vert) if mesh_vert else np.zeros((0, 3)))
+
+
+def _may_collide(ga: _CollGeom, gc: _CollGeom, links: List[_Link], bodies: List[_Body], excl) -> bool:
+    """MuJoCo's filters: same weld body, parent-child weld bodies unless the parent is the world, <exclude>, contype/conaffinity."""
+    la, lc = ga.link, gc.link
+    if la == lc:
+        return False
+    if (links[la].parent == lc and lc != 0) or (links[lc].parent == la and la != 0):
+        return False
+    if frozenset((bodies[ga.body].name, bodies[gc.body].name)) in excl:
+        return False
+    return bool((ga.geom.contype & gc.geom.conaffinity) or (gc.geom.contype & ga.geom.conaffinity))
+
+
+def candidate_pairs(geoms: List[_CollGeom], links: List[_Link], bodies: List[_Body], excludes) -> List[_Pair]:
+    """The static candidate list, the geom of the lower type first, with the pair's mixed contact parameters."""
+    excl = {frozenset(e) for e in excludes}
+    pairs = []
+    for a in range(len(geoms)):
+        for c in range(a + 1, len(geoms)):
+            if not _may_collide(geoms[a], geoms[c], links, bodies, excl):
+                continue
+            g1, g2 = (a, c) if geoms[a].geom.type <= geoms[c].geom.type else (c, a)
+            A, B = geoms[g1].geom, geoms[g2].geom
+            if A.type == GEOM_PLANE:
+                fn = FN_PLANE_BOX if B.type == GEOM_BOX else FN_PLANE_CONVEX
+            elif A.type == GEOM_BOX and B.type == GEOM_BOX:
+                fn = FN_BOX_BOX
+            else:
+                fn = FN_CONVEX
+            fr = np.maximum(A.friction, B.friction)
+            pairs.append(_Pair(g1=g1, g2=g2, fn=fn, condim=max(A.condim, B.condim),
+                               friction=np.array([fr[0], fr[0], fr[1], fr[2], fr[2]]),
+                               solref=0.5 * (A.solref + B.solref), solimp=0.5 * (A.solimp + B.solimp)))
+    return pairs
+
+
+def pair_slots(pairs: List[_Pair], plane_convex_points: int) -> np.ndarray:
+    """First contact slot of every pair (and, last, their number)."""
+    slot = np.zeros(len(pairs) + 1, dtype=np.int32)
+    for i, p in enumerate(pairs):
+        slot[i + 1] = slot[i] + (plane_convex_points if p.fn == FN_PLANE_CONVEX else FN_MAXCON[p.fn])
+    return slot
+
+
+def _act_range(a, key, flag):
+    if a.get(flag, "false") != "true" or a.get(key) is None:
+        return [-UNLIMITED, UNLIMITED]
+    return _vec(a.get(key), 2, [0, 0])
+
+
+def actuator_tables(acts, joints: List[_JointAddr]) -> Dict[str, np.ndarray]:
+    joint_names = [j.name for j in joints]
+    # MuJoCo clamps ctrl / actuator force only when ctrllimited / forcelimited is set (world.xml:104-124 sets both on all seven
+    # actuators); an unlimited actuator gets an effectively infinite range so that the kernels' unconditional clamp is a no-op
+    return dict(
+        act_dof=np.array([joints[joint_names.index(a.get("joint"))].dofadr for a in acts], dtype=np.int32),
+        act_gear=np.array([float(a.get("gear", 1)) for a in acts]),
+        act_kp=np.array([float(a.get("kp", 1)) for a in acts]),
+        act_ctrlrange=np.array([_act_range(a, "ctrlrange", "ctrllimited") for a in acts], dtype=np.float64).reshape(-1, 2),
+        act_forcerange=np.array([_act_range(a, "forcerange", "forcelimited") for a in acts], dtype=np.float64).reshape(-1, 2))
+
+
+def buffer_caps(nv: int):
+    """-> (nconmax, njmax).  Device-friendly buffer caps (the XML asks for nconmax=100 njmax=500, world.xml:44, which MuJoCo only
+    uses as buffer sizes): contacts beyond nconmax / rows beyond njmax are dropped identically by the
+    oracle and the HIP path.  One lane group (16 or 32 lanes) serves an env, so caps are multiples of it."""
+    group = 16 if nv <= 16 else 32
+    eff_nconmax = group
+    # 32-lane models: 124 rows - measured on cfg4 (8192 envs x 300 env-steps of the bench: 7.4e8 env-substeps) 3.1e5 substeps wanted 97-104 rows,
+    # 8.9e3 105-112, 1.4e3 113-120, 24 121-128, 1 more: with 124 fewer than 4e-8 of the env-substeps drop a row (96 rows: 4.3e-4); 124 is what
+    # the 20 KB of LDS per workgroup hold once the pair / geom tables are read from global memory (persist.h: TG)
+    eff_njmax = {True: 48, False: 124}[nv <= 16]
+    return eff_nconmax, eff_njmax
+
+
+def _link_dofmask(lk: _Link, dofs: List[_Dof]) -> int:
+    """bit k is set when dof k lies on the path from the link to the root"""
+    mask, k = 0, lk.dofadr + lk.dofnum - 1
+    while k >= 0:
+        mask |= (1 << k)
+        k = dofs[k].parent
+    return mask
+
+
+def assemble_arrays(bodies, fold: _Fold, dofs: List[_Dof], qpos0, geoms: List[_CollGeom], mesh_vert, pairs: List[_Pair], slot,
+                    act: Dict[str, np.ndarray], opt: dict) -> Dict[str, np.ndarray]:
+    """The blob's tables (model.py: _ARRAY_FIELDS), one comprehension per field; the qpos0 statistics are filled in afterwards."""
+    links, nv, ngeom, npair = fold.links, len(dofs), len(geoms), len(pairs)
+    i32 = dict(dtype=np.int32)
+    arrays = dict(
+        qpos0=np.array(qpos0),
+        link_dofmask=np.array([_link_dofmask(lk, dofs) for lk in links], **i32),
+        link_parent=np.array([lk.parent for lk in links], **i32),
+        link_pos=np.array([lk.pos for lk in links]), link_quat=np.array([lk.quat for lk in links]),
+        link_dofadr=np.array([lk.dofadr for lk in links], **i32), link_dofnum=np.array([lk.dofnum for lk in links], **i32),
+        link_qposadr=np.array([lk.qposadr for lk in links], **i32), link_free=np.array([lk.free for lk in links], **i32),
+        link_mass=np.array([lk.inertial.mass for lk in links], dtype=np.float64), link_com=np.array([lk.inertial.com for lk in links]),
+        link_inertia=np.array([[I[0, 0], I[1, 1], I[2, 2], I[0, 1], I[0, 2], I[1, 2]] for I in (lk.inertial.inertia for lk in links)]),
+        dof_link=np.array([d.link for d in dofs], **i32), dof_type=np.array([d.type for d in dofs], **i32),
+        dof_axis=np.array([d.axis for d in dofs]).reshape(nv, 3), dof_pos=np.array([d.pos for d in dofs]).reshape(nv, 3),
+        dof_parent=np.array([d.parent for d in dofs], **i32), dof_damping=np.array([d.damping for d in dofs]),
+        dof_qposadr=np.array([d.qposadr for d in dofs], **i32),
+        dof_invweight0=np.zeros(nv), dof_limited=np.array([d.limited for d in dofs], **i32),
+        dof_range=np.array([d.range for d in dofs]).reshape(nv, 2),
+        dof_solref=np.tile([0.02, 1.0], (nv, 1)), dof_solimp=np.tile([0.9, 0.95, 0.001, 0.5, 2.0], (nv, 1)),
+        body_link=fold.body_link, body_pos=fold.body_pos, body_quat=fold.body_quat,
+        body_mocap=np.array([int(b.mocap) for b in bodies], **i32),
+        geom_type=np.array([g.geom.type for g in geoms], **i32),
+        geom_link=np.array([g.link for g in geoms], **i32),
+        geom_body=np.array([g.body for g in geoms], **i32),
+        geom_pos=np.array([g.pos for g in geoms]), geom_quat=np.array([g.quat for g in geoms]),
+        geom_size=np.array([g.shape.size for g in geoms]), geom_rbound=np.array([g.shape.rbound for g in geoms]),
+        geom_condim=np.array([g.geom.condim for g in geoms], **i32),
+        geom_meshadr=np.array([g.meshadr for g in geoms], **i32),
+        geom_meshnum=np.array([g.meshnum for g in geoms], **i32),
+        geom_invweight=np.zeros((ngeom, 2)),
+        geom_aabb=np.array([g.shape.aabb for g in geoms]).reshape(ngeom, 6),
+        mesh_vert=mesh_vert,
+        pair_geom1=np.array([p.g1 for p in pairs], **i32),
+        pair_geom2=np.array([p.g2 for p in pairs], **i32),
+        pair_fn=np.array([p.fn for p in pairs], **i32),
+        pair_condim=np.array([p.condim for p in pairs], **i32),
+        pair_slot=slot,
+        pair_friction=np.array([p.friction for p in pairs]).reshape(npair, 5),
+        pair_solref=np.array([p.solref for p in pairs]).reshape(npair, 2),
+        pair_solimp=np.array([p.solimp for p in pairs]).reshape(npair, 5),
+        **act,
+    )
+    sizes = np.zeros(16, dtype=np.int32)
+    sizes[[SZ_NQ, SZ_NV, SZ_NU, SZ_NLINK, SZ_NBODY, SZ_NGEOM, SZ_NPAIR, SZ_NMESHVERT, SZ_NSLOT,
+           SZ_NLIMIT, SZ_NCONMAX, SZ_NJMAX, SZ_NMOCAP]] = [
+        len(qpos0), nv, len(act["act_dof"]), len(links), len(bodies), ngeom, npair, len(mesh_vert), slot[-1],
+        sum(d.limited for d in dofs), opt["nconmax"], opt["njmax"], sum(b.mocap for b in bodies)]
+    optv = np.zeros(16)
+    optv[[OPT_TIMESTEP, OPT_IMPRATIO, OPT_GRAV_Z, OPT_TOLERANCE, OPT_ITERATIONS, OPT_LS_ITERATIONS,
+          OPT_LS_TOLERANCE, OPT_MPR_TOLERANCE, OPT_MPR_ITERATIONS]] = [
+        opt["timestep"], opt["impratio"], -9.81, 1e-8, 100, 50, 0.01, 1e-6, 50]
+    arrays["sizes"], arrays["opt"] = sizes, optv
+    return arrays
+
+
+def _count_dense_dofs(model: Model) -> int:
+    """dofs >= ndense never couple to another dof in M (e.g. a free box with its COM at the body origin):
+    the cooperative Cholesky skips their off-diagonal updates when factoring M and M + h B"""
+    rs = np.random.default_rng(0)
+    dense = 0
+    for _ in range(4):
+        qr = model.qpos0.copy()
+        qr[:model.nu] += rs.uniform(-0.3, 0.3, model.nu)
+        for l in range(1, model.nlink):
+            if model.link_free[l]:
+                a = model.link_qposadr[l]
+                qr[a + 3:a + 7] = quat_normalize(rs.normal(size=4))
+        Mr = mass_matrix(model, qr)
+        off = np.abs(Mr - np.diag(np.diag(Mr))) > 1e-12
+        idx = np.where(off.any(axis=0))[0]
+        dense = max(dense, int(idx.max()) + 1 if idx.size else 0)
+    return dense
+
+
+def _body_invweights(model: Model, Minv, inertials: List[_MassProps]) -> np.ndarray:
+    """Per body (translational, rotational): mean diagonal of J M^-1 J^T at the body's centre of mass, at qpos0."""
+    xpos, xquat = link_kinematics(model, model.qpos0)
+    ang, lin, anchor = dof_motion(model, xpos, xquat, model.qpos0)
+    body_invw = np.zeros((model.nbody, 2))
+    for i in range(1, model.nbody):
+        l = model.body_link[i]
+        if l == 0:
             continue
-        # joints applied in order: axis of joint d is expressed in the frame *after* earlier
-        # joints of the same body; for this model a body never mixes hinges (all slides or one
-        # hinge), so the final link frame gives the same axes.
-        for d in range(m.link_dofadr[l], m.link_dofadr[l] + m.link_dofnum[l]):
-            ax = R @ m.dof_axis[d]
-            if m.dof_type[d] == DOF_SLIDE:
-                lin[d] = ax
-            else:
-                ang[d] = ax
-                anchor[d] = xpos[l] + R @ m.dof_pos[d]
-    return ang, lin, anchor
+        Rl = quat_to_mat(xquat[l])
+        c = xpos[l] + Rl @ (model.body_pos[i] + quat_to_mat(model.body_quat[i]) @ inertials[i].com)
+        jp, jr = point_jacobian(model, ang, lin, anchor, l, c)
+        body_invw[i, 0] = np.trace(jp @ Minv @ jp.T) / 3.0
+        body_invw[i, 1] = np.trace(jr @ Minv @ jr.T) / 3.0
+    return body_invw
 
 
-def point_jacobian(m: Model, ang, lin, anchor, link: int, point):
-    """jacp[3,nv], jacr[3,nv] of a world point rigidly attached to ``link``."""
-    jp = np.zeros((3, m.nv)); jr = np.zeros((3, m.nv))
-    if link == 0:
-        return jp, jr
-    d = m.link_dofadr[link] + m.link_dofnum[link] - 1
-    while d >= 0:
-        jr[:, d] = ang[d]
-        jp[:, d] = lin[d] + np.cross(ang[d], point - anchor[d])
-        d = m.dof_parent[d]
-    return jp, jr
+def fill_qpos0_statistics(model: Model, inertials: List[_MassProps]):
+    """mj_setConst: meaninertia, dof and body inverse weights at qpos0 (used by the constraint regulariser), and ndense."""
+    M0 = mass_matrix(model, model.qpos0)
+    Minv = np.linalg.inv(M0)
+    model.opt[OPT_MEANINERTIA] = np.trace(M0) / model.nv
+    dinv = np.diag(Minv).copy()
+    for l in range(1, model.nlink):
+        if model.link_free[l]:
+            a = model.link_dofadr[l]
+            dinv[a:a + 3] = dinv[a:a + 3].mean(); dinv[a + 3:a + 6] = dinv[a + 3:a + 6].mean()
+    model.dof_invweight0[:] = dinv
+    model.sizes[SZ_NDENSE] = _count_dense_dofs(model)
+    body_invw = _body_invweights(model, Minv, inertials)
+    model.geom_invweight[:] = body_invw[model.geom_body]
+    model.meta["body_invweight0"] = body_invw.tolist()
+    model.meta["link_mass"] = model.link_mass.tolist()
 
 
-def mass_matrix(m: Model, qpos):
-    xpos, xquat = link_kinematics(m, qpos)
-    ang, lin, anchor = dof_motion(m, xpos, xquat, qpos)
-    M = np.zeros((m.nv, m.nv))
-    for l in range(1, m.nlink):
-        R = quat_to_mat(xquat[l])
-        c = xpos[l] + R @ m.link_com[l]
-        ixx, iyy, izz, ixy, ixz, iyz = m.link_inertia[l]
-        I = R @ np.array([[ixx, ixy, ixz], [ixy, iyy, iyz], [ixz, iyz, izz]]) @ R.T
-        jp, jr = point_jacobian(m, ang, lin, anchor, l, c)
-        M += m.link_mass[l] * jp.T @ jp + jr.T @ I @ jr
-    return M
-
-
-# ----------------------------------------------------------------------------- compile
 def compile_model(dofs: Sequence[str] = ("slide_x", "slide_y"), n_blocks: int = 0,
                   block_pos: Optional[np.ndarray] = None, xml_file: str = "models/world.xml",
                   ref_root: Path = DEFAULT_REF_ROOT, set_xml: Sequence = (), block_geom: Optional[dict] = None,
                   plane_convex_points: int = 1) -> Model:
     """plane_convex_points: contacts a plane <-> convex (mesh / cylinder) pair may hold - 1: the deepest support point only (the committed
     reference configurations); 4: up to three more around it, as MuJoCo's mjc_PlaneConvex adds them (oracle/hsr_oracle.c)."""
-    ref_root = Path(ref_root)
     assert plane_convex_points in (1, 4)
-    if block_pos is None:
-        # resting height on the pan: 0.405 + 0.017 (world.xml:83-84, util.py:120)
-        block_pos = np.array([[0.0, 0.12 * (i - (n_blocks - 1) / 2.0), 0.422]
-                              for i in range(n_blocks)]).reshape(n_blocks, 3)
-    block_pos = np.asarray(block_pos, dtype=np.float64).reshape(n_blocks, 3)
+    xml_path = Path(ref_root) / xml_file
     set_xml = [(str(p), str(v)) for p, v in set_xml]
-    parsed = _parse_tree(ref_root, xml_file, list(dofs), n_blocks, block_pos, set_xml, block_geom)
-    bodies: List[_Body] = parsed["bodies"]
-    opt = parsed["opt"]
-    meta = dict(parsed["meta"])
+    root, acts = _mutated_tree(xml_path, list(dofs), _block_positions(block_pos, n_blocks), set_xml, block_geom)
+    parsed = _read_tree(root, xml_path)
+    bodies, opt, meta = parsed.bodies, parsed.opt, parsed.meta
     if set_xml:
         meta.update(set_xml=[list(c) for c in set_xml])
     meta.update(plane_convex_points=int(plane_convex_points))
@@ -577,360 +814,29 @@ def compile_model(dofs: Sequence[str] = ("slide_x", "slide_y"), n_blocks: int = 
                 decisions="H1 malformed pos->0; H2 inertiafromgeom all geoms density 1000 (legacy "
                           "mesh inertia); H3 default class 'all' is global; H4 hinge ranges in "
                           "degrees; H5 quats normalised; H6 goal is mocap; H7 MuJoCo 2.0 defaults")
-    nb = len(bodies)
 
-    # ---- per-mesh data -----------------------------------------------------------------------
-    mesh_cache: Dict[str, dict] = {}
-
-    def mesh_data(name):
-        if name not in mesh_cache:
-            tris = load_stl(parsed["meshes"][name])
-            V, com, I = mesh_inertia_legacy(tris)
-            hull = convex_hull_vertices(tris.reshape(-1, 3))
-            mesh_cache[name] = dict(V=V, com=com, I=I, hull=hull)
-        return mesh_cache[name]
-
-    # ---- body inertias in body frame (H2) --------------------------------------------------------
-    def geom_inertia(g: _Geom):
-        """-> (mass, com in body frame, inertia about com in body frame)"""
-        Rg = quat_to_mat(g.quat)
-        if g.type == GEOM_PLANE:
-            return 0.0, np.zeros(3), np.zeros((3, 3))
-        if g.type == GEOM_MESH:
-            md = mesh_data(g.mesh)
-            vol, c, I = md["V"], md["com"], md["I"]
-        elif g.type == GEOM_BOX:
-            a, b, c_ = g.size
-            vol = 8 * a * b * c_
-            I = vol / 3.0 * np.diag([b * b + c_ * c_, a * a + c_ * c_, a * a + b * b]); c = np.zeros(3)
-        elif g.type == GEOM_SPHERE:
-            r = g.size[0]
-            vol = 4.0 / 3.0 * np.pi * r ** 3
-            I = 0.4 * vol * r * r * np.eye(3); c = np.zeros(3)
-        elif g.type == GEOM_CYLINDER:
-            r, hh = g.size[0], g.size[1]
-            vol = np.pi * r * r * 2 * hh
-            ixx = vol * (3 * r * r + 4 * hh * hh) / 12.0
-            I = np.diag([ixx, ixx, 0.5 * vol * r * r]); c = np.zeros(3)
-        else:
-            raise ValueError(g.type)
-        mass = g.mass if g.mass is not None else g.density * vol
-        scale = mass / vol
-        return mass, g.pos + Rg @ c, Rg @ (I * scale) @ Rg.T
-
-    body_mass = np.zeros(nb); body_com = np.zeros((nb, 3)); body_I = np.zeros((nb, 3, 3))
-    for i, b in enumerate(bodies):
-        if i == 0:
-            continue
-        parts = [geom_inertia(g) for g in b.geoms] if parsed["inertiafromgeom"] else []
-        parts = [p for p in parts if p[0] > 0]
-        if parts:
-            mtot = sum(p[0] for p in parts)
-            com = sum(p[0] * p[1] for p in parts) / mtot
-            I = np.zeros((3, 3))
-            for mm, c, Ic in parts:
-                d = c - com
-                I += Ic + mm * (d @ d * np.eye(3) - np.outer(d, d))
-            body_mass[i], body_com[i], body_I[i] = mtot, com, I
-        elif b.inertial is not None:
-            Ri = quat_to_mat(b.inertial["quat"])
-            body_mass[i] = b.inertial["mass"]
-            body_com[i] = b.inertial["pos"]
-            body_I[i] = Ri @ np.diag(b.inertial["diag"]) @ Ri.T
-
-    # ---- fold joint-less bodies into links ---------------------------------------------------------
-    body_link = np.zeros(nb, dtype=np.int32)
-    body_lpos = np.zeros((nb, 3)); body_lquat = np.tile([1., 0, 0, 0], (nb, 1))
-    links = [dict(body=0, parent=0, pos=np.zeros(3), quat=np.array([1., 0, 0, 0]))]
-    for i in range(1, nb):
-        b = bodies[i]
-        p = b.parent
-        # pose of this body in its parent's link frame
-        Rp = quat_to_mat(body_lquat[p])
-        pos_in_l = body_lpos[p] + Rp @ b.pos
-        quat_in_l = quat_normalize(quat_mul(body_lquat[p], b.quat))
-        if b.joints:
-            links.append(dict(body=i, parent=int(body_link[p]), pos=pos_in_l, quat=quat_in_l))
-            body_link[i] = len(links) - 1
-        else:
-            body_link[i] = body_link[p]
-            body_lpos[i], body_lquat[i] = pos_in_l, quat_in_l
-    nlink = len(links)
-
-    link_mass = np.zeros(nlink); link_com = np.zeros((nlink, 3)); link_I = np.zeros((nlink, 3, 3))
-    for l in range(1, nlink):
-        members = [i for i in range(nb) if body_link[i] == l and body_mass[i] > 0]
-        mtot = sum(body_mass[i] for i in members)
-        coms = {i: body_lpos[i] + quat_to_mat(body_lquat[i]) @ body_com[i] for i in members}
-        com = sum(body_mass[i] * coms[i] for i in members) / mtot
-        I = np.zeros((3, 3))
-        for i in members:
-            Rb = quat_to_mat(body_lquat[i])
-            d = coms[i] - com
-            I += Rb @ body_I[i] @ Rb.T + body_mass[i] * (d @ d * np.eye(3) - np.outer(d, d))
-        link_mass[l], link_com[l], link_I[l] = mtot, com, I
-
-    # ---- dofs -----------------------------------------------------------------------------------------
-    dof = dict(link=[], type=[], axis=[], pos=[], parent=[], damping=[], qposadr=[], limited=[],
-               range=[])
-    link_dofadr = np.zeros(nlink, dtype=np.int32); link_dofnum = np.zeros(nlink, dtype=np.int32)
-    link_qposadr = np.zeros(nlink, dtype=np.int32); link_free = np.zeros(nlink, dtype=np.int32)
-    joint_names, joint_qposadr, joint_dofadr = [], [], []
-    qpos0 = []
-    last_dof_of_link = {0: -1}
-    for l in range(1, nlink):
-        b = bodies[links[l]["body"]]
-        link_dofadr[l] = len(dof["link"]); link_qposadr[l] = len(qpos0)
-        prev = last_dof_of_link[links[l]["parent"]]
-        for j in b.joints:
-            joint_names.append(j.name)
-            if j.type == "free":
-                assert len(b.joints) == 1 and links[l]["parent"] == 0
-                link_free[l] = 1
-                joint_qposadr.append((len(qpos0), 7)); joint_dofadr.append(len(dof["link"]))
-                qa = len(qpos0)
-                qpos0 += list(links[l]["pos"]) + list(links[l]["quat"])
-                for k in range(6):
-                    dof["link"].append(l); dof["type"].append(DOF_FREE_LIN if k < 3 else DOF_FREE_ANG)
-                    dof["axis"].append(np.eye(3)[k % 3]); dof["pos"].append(np.zeros(3))
-                    dof["parent"].append(prev); prev = len(dof["link"]) - 1
-                    # translational dofs address qpos[qa+k]; rotational ones the quaternion start
-                    dof["damping"].append(0.0); dof["qposadr"].append(qa + k if k < 3 else qa + 3)
-                    dof["limited"].append(0); dof["range"].append(np.zeros(2))
-            else:
-                joint_qposadr.append((len(qpos0), 1)); joint_dofadr.append(len(dof["link"]))
-                dof["link"].append(l); dof["type"].append(DOF_SLIDE if j.type == "slide" else DOF_HINGE)
-                dof["axis"].append(j.axis); dof["pos"].append(j.pos); dof["parent"].append(prev)
-                prev = len(dof["link"]) - 1
-                dof["damping"].append(j.damping); dof["qposadr"].append(len(qpos0))
-                dof["limited"].append(int(j.limited)); dof["range"].append(j.range)
-                qpos0.append(0.0)
-        link_dofnum[l] = len(dof["link"]) - link_dofadr[l]
-        last_dof_of_link[l] = prev
-    nv, nq = len(dof["link"]), len(qpos0)
-    # a non-free link may hold several slides or exactly one hinge (keeps dof axes = final frame)
-    for l in range(1, nlink):
-        types = [dof["type"][d] for d in range(link_dofadr[l], link_dofadr[l] + link_dofnum[l])]
-        assert link_free[l] or types.count(DOF_HINGE) == 0 or len(types) == 1, "mixed joints on a body"
-
-    # ---- geoms (collidable only) -------------------------------------------------------------------------
-    g_rec = []
-    mesh_vert = []
-    geom_names = []
-    for i, b in enumerate(bodies):
-        for g in b.geoms:
-            if g.contype == 0 and g.conaffinity == 0:
-                continue
-            Rb = quat_to_mat(body_lquat[i])
-            pos = body_lpos[i] + Rb @ g.pos
-            quat = quat_normalize(quat_mul(body_lquat[i], g.quat))
-            meshadr, meshnum = 0, 0
-            if g.type == GEOM_MESH:
-                md = mesh_data(g.mesh)
-                # geom frame origin := mesh centre of mass (MuJoCo recentres meshes)
-                verts = md["hull"] - md["com"]
-                pos = pos + quat_to_mat(quat) @ md["com"]
-                meshadr, meshnum = sum(len(v) for v in mesh_vert), len(verts)
-                mesh_vert.append(verts)
-                rbound = np.linalg.norm(verts, axis=1).max()
-                size = np.abs(verts).max(0)
-            elif g.type == GEOM_BOX:
-                rbound = np.linalg.norm(g.size); size = g.size
-            elif g.type == GEOM_CYLINDER:
-                rbound = np.hypot(g.size[0], g.size[1]); size = g.size
-            elif g.type == GEOM_SPHERE:
-                rbound = g.size[0]; size = g.size
-            else:
-                rbound = 0.0; size = g.size
-            # box containing the geom in its own frame: centre(3) + half extents(3); tight (asymmetric) for hulls
-            if g.type == GEOM_MESH:
-                lo_, hi_ = verts.min(0), verts.max(0)
-                aabb = np.concatenate([(lo_ + hi_) / 2, (hi_ - lo_) / 2])
-            elif g.type == GEOM_CYLINDER:
-                aabb = np.array([0, 0, 0, g.size[0], g.size[0], g.size[1]])
-            elif g.type == GEOM_SPHERE:
-                aabb = np.array([0, 0, 0, g.size[0], g.size[0], g.size[0]])
-            elif g.type == GEOM_BOX:
-                aabb = np.concatenate([np.zeros(3), g.size])
-            else:
-                aabb = np.zeros(6)
-            g_rec.append(dict(type=g.type, link=int(body_link[i]), body=i, pos=pos, quat=quat, aabb=aabb,
-                              size=size, rbound=rbound, condim=g.condim, meshadr=meshadr,
-                              meshnum=meshnum, g=g))
-            geom_names.append(g.name if g.mesh is None else f"{b.name}:{g.mesh}")
-    ngeom = len(g_rec)
-    mesh_vert = np.concatenate(mesh_vert) if mesh_vert else np.zeros((0, 3))
-
-    # ---- candidate pairs ---------------------------------------------------------------------------------------
-    link_parent = np.array([lk["parent"] for lk in links], dtype=np.int32)
-    excl = {frozenset(e) for e in parsed["excludes"]}
-    pairs = []
-    for a in range(ngeom):
-        for c in range(a + 1, ngeom):
-            ga, gc = g_rec[a], g_rec[c]
-            la, lc = ga["link"], gc["link"]
-            if la == lc:
-                continue
-            if (link_parent[la] == lc and lc != 0) or (link_parent[lc] == la and la != 0):
-                continue
-            if frozenset((bodies[ga["body"]].name, bodies[gc["body"]].name)) in excl:
-                continue
-            if not ((ga["g"].contype & gc["g"].conaffinity) or (gc["g"].contype & ga["g"].conaffinity)):
-                continue
-            g1, g2 = (a, c) if ga["type"] <= gc["type"] else (c, a)
-            t1, t2 = g_rec[g1]["type"], g_rec[g2]["type"]
-            if t1 == GEOM_PLANE:
-                fn = FN_PLANE_BOX if t2 == GEOM_BOX else FN_PLANE_CONVEX
-            elif t1 == GEOM_BOX and t2 == GEOM_BOX:
-                fn = FN_BOX_BOX
-            else:
-                fn = FN_CONVEX
-            A, B = g_rec[g1]["g"], g_rec[g2]["g"]
-            fr = np.maximum(A.friction, B.friction)
-            pairs.append(dict(g1=g1, g2=g2, fn=fn, condim=max(A.condim, B.condim),
-                              friction=np.array([fr[0], fr[0], fr[1], fr[2], fr[2]]),
-                              solref=0.5 * (A.solref + B.solref), solimp=0.5 * (A.solimp + B.solimp)))
-    npair = len(pairs)
-    slot = np.zeros(npair + 1, dtype=np.int32)
-    for i, p in enumerate(pairs):
-        slot[i + 1] = slot[i] + (plane_convex_points if p["fn"] == FN_PLANE_CONVEX else FN_MAXCON[p["fn"]])
-
-    # ---- actuators -------------------------------------------------------------------------------------------------
-    acts = parsed["actuators"]
-    act_dof = np.array([joint_dofadr[joint_names.index(a.get("joint"))] for a in acts], dtype=np.int32)
-    act_gear = np.array([float(a.get("gear", 1)) for a in acts])
-    act_kp = np.array([float(a.get("kp", 1)) for a in acts])
-    # MuJoCo clamps ctrl / actuator force only when ctrllimited / forcelimited is set (world.xml:104-124 sets both on all seven
-    # actuators); an unlimited actuator gets an effectively infinite range so that the kernels' unconditional clamp is a no-op
-    def _range(a, key, flag):
-        if a.get(flag, "false") != "true" or a.get(key) is None:
-            return [-UNLIMITED, UNLIMITED]
-        return _vec(a.get(key), 2, [0, 0])
-    act_ctrlrange = np.array([_range(a, "ctrlrange", "ctrllimited") for a in acts], dtype=np.float64).reshape(-1, 2)
-    act_forcerange = np.array([_range(a, "forcerange", "forcelimited") for a in acts], dtype=np.float64).reshape(-1, 2)
-
-    # bit k of link_dofmask[l] is set when dof k lies on the path from link l to the root
-    link_dofmask = np.zeros(nlink, dtype=np.int32)
-    for l in range(1, nlink):
-        k = link_dofadr[l] + link_dofnum[l] - 1
-        while k >= 0:
-            link_dofmask[l] |= (1 << k)
-            k = dof["parent"][k]
-    # device-friendly buffer caps (the XML asks for nconmax=100 njmax=500, world.xml:44, which MuJoCo only
-    # uses as buffer sizes): contacts beyond nconmax / rows beyond njmax are dropped identically by the
-    # oracle and the HIP path.  One lane group (16 or 32 lanes) serves an env, so caps are multiples of it.
-    group = 16 if nv <= 16 else 32
-    eff_nconmax = group
-    # 32-lane models: 124 rows - measured on cfg4 (8192 envs x 300 env-steps of the bench: 7.4e8 env-substeps) 3.1e5 substeps wanted 97-104 rows,
-    # 8.9e3 105-112, 1.4e3 113-120, 24 121-128, 1 more: with 124 fewer than 4e-8 of the env-substeps drop a row (96 rows: 4.3e-4); 124 is what
-    # the 20 KB of LDS per workgroup hold once the pair / geom tables are read from global memory (persist.h: TG)
-    eff_njmax = {True: 48, False: 124}[nv <= 16]
+    meshes = _MeshCache(parsed.meshes)
+    inertials = body_inertias(bodies, parsed.inertiafromgeom, meshes)
+    fold = fold_links(bodies, inertials)
+    dof_recs, qpos0, joints = assign_dofs(bodies, fold.links)
+    geoms, mesh_vert = collidable_geoms(bodies, fold, meshes)
+    pairs = candidate_pairs(geoms, fold.links, bodies, parsed.excludes)
+    slot = pair_slots(pairs, plane_convex_points)
+    act = actuator_tables(acts, joints)
     meta["xml_nconmax_njmax"] = [opt["nconmax"], opt["njmax"]]
-    opt["nconmax"], opt["njmax"] = eff_nconmax, eff_njmax
-
-    arrays = dict(
-        qpos0=np.array(qpos0),
-        link_dofmask=link_dofmask,
-        link_parent=link_parent,
-        link_pos=np.array([lk["pos"] for lk in links]), link_quat=np.array([lk["quat"] for lk in links]),
-        link_dofadr=link_dofadr, link_dofnum=link_dofnum, link_qposadr=link_qposadr, link_free=link_free,
-        link_mass=link_mass, link_com=link_com,
-        link_inertia=np.array([[I[0, 0], I[1, 1], I[2, 2], I[0, 1], I[0, 2], I[1, 2]] for I in link_I]),
-        dof_link=np.array(dof["link"], dtype=np.int32), dof_type=np.array(dof["type"], dtype=np.int32),
-        dof_axis=np.array(dof["axis"]).reshape(nv, 3), dof_pos=np.array(dof["pos"]).reshape(nv, 3),
-        dof_parent=np.array(dof["parent"], dtype=np.int32), dof_damping=np.array(dof["damping"]),
-        dof_qposadr=np.array(dof["qposadr"], dtype=np.int32),
-        dof_invweight0=np.zeros(nv), dof_limited=np.array(dof["limited"], dtype=np.int32),
-        dof_range=np.array(dof["range"]).reshape(nv, 2),
-        dof_solref=np.tile([0.02, 1.0], (nv, 1)), dof_solimp=np.tile([0.9, 0.95, 0.001, 0.5, 2.0], (nv, 1)),
-        body_link=body_link, body_pos=body_lpos, body_quat=body_lquat,
-        body_mocap=np.array([int(b.mocap) for b in bodies], dtype=np.int32),
-        geom_type=np.array([g["type"] for g in g_rec], dtype=np.int32),
-        geom_link=np.array([g["link"] for g in g_rec], dtype=np.int32),
-        geom_body=np.array([g["body"] for g in g_rec], dtype=np.int32),
-        geom_pos=np.array([g["pos"] for g in g_rec]), geom_quat=np.array([g["quat"] for g in g_rec]),
-        geom_size=np.array([g["size"] for g in g_rec]), geom_rbound=np.array([g["rbound"] for g in g_rec]),
-        geom_condim=np.array([g["condim"] for g in g_rec], dtype=np.int32),
-        geom_meshadr=np.array([g["meshadr"] for g in g_rec], dtype=np.int32),
-        geom_meshnum=np.array([g["meshnum"] for g in g_rec], dtype=np.int32),
-        geom_invweight=np.zeros((ngeom, 2)),
-        geom_aabb=np.array([g["aabb"] for g in g_rec]).reshape(ngeom, 6),
-        mesh_vert=mesh_vert,
-        pair_geom1=np.array([p["g1"] for p in pairs], dtype=np.int32),
-        pair_geom2=np.array([p["g2"] for p in pairs], dtype=np.int32),
-        pair_fn=np.array([p["fn"] for p in pairs], dtype=np.int32),
-        pair_condim=np.array([p["condim"] for p in pairs], dtype=np.int32),
-        pair_slot=slot,
-        pair_friction=np.array([p["friction"] for p in pairs]).reshape(npair, 5),
-        pair_solref=np.array([p["solref"] for p in pairs]).reshape(npair, 2),
-        pair_solimp=np.array([p["solimp"] for p in pairs]).reshape(npair, 5),
-        act_dof=act_dof, act_gear=act_gear, act_kp=act_kp, act_ctrlrange=act_ctrlrange,
-        act_forcerange=act_forcerange,
-    )
-    sizes = np.zeros(16, dtype=np.int32)
-    sizes[[SZ_NQ, SZ_NV, SZ_NU, SZ_NLINK, SZ_NBODY, SZ_NGEOM, SZ_NPAIR, SZ_NMESHVERT, SZ_NSLOT,
-           SZ_NLIMIT, SZ_NCONMAX, SZ_NJMAX, SZ_NMOCAP]] = [
-        nq, nv, len(acts), nlink, nb, ngeom, npair, len(mesh_vert), slot[-1],
-        int(np.sum(dof["limited"])), opt["nconmax"], opt["njmax"], sum(b.mocap for b in bodies)]
-    optv = np.zeros(16)
-    optv[[OPT_TIMESTEP, OPT_IMPRATIO, OPT_GRAV_Z, OPT_TOLERANCE, OPT_ITERATIONS, OPT_LS_ITERATIONS,
-          OPT_LS_TOLERANCE, OPT_MPR_TOLERANCE, OPT_MPR_ITERATIONS]] = [
-        opt["timestep"], opt["impratio"], -9.81, 1e-8, 100, 50, 0.01, 1e-6, 50]
-    arrays["sizes"], arrays["opt"] = sizes, optv
+    opt["nconmax"], opt["njmax"] = buffer_caps(len(dof_recs))
     assert opt["cone"] == "elliptic", "only the reference's elliptic cones are implemented"
+    arrays = assemble_arrays(bodies, fold, dof_recs, qpos0, geoms, mesh_vert, pairs, slot, act, opt)
 
-    names = dict(body=[b.name for b in bodies], joint=joint_names, geom=geom_names,
+    names = dict(body=[b.name for b in bodies], joint=[j.name for j in joints], geom=[g.name for g in geoms],
                  actuator=[a.get("name") for a in acts],
-                 link=[bodies[lk["body"]].name for lk in links])
-    meta["joint_qposadr"] = joint_qposadr
-    meta["joint_dofadr"] = joint_dofadr
+                 link=[bodies[lk.body].name for lk in fold.links])
+    meta["joint_qposadr"] = [(j.qposadr, j.nq) for j in joints]
+    meta["joint_dofadr"] = [j.dofadr for j in joints]
     meta["mesh_license"] = ("hull vertices derived from hsr/hsr_meshes (Toyota, CC BY-NC-ND 4.0, "
                             "hsr/hsr_meshes/LICENSE.txt); kept only as collision tables")
     model = Model(arrays=arrays, names=names, meta=meta)
-
-    # ---- qpos0 statistics (mj_setConst) ------------------------------------------------------------------------------
-    q0 = arrays["qpos0"]
-    M0 = mass_matrix(model, q0)
-    Minv = np.linalg.inv(M0)
-    optv[OPT_MEANINERTIA] = np.trace(M0) / nv
-    dinv = np.diag(Minv).copy()
-    for l in range(1, nlink):
-        if link_free[l]:
-            a = link_dofadr[l]
-            dinv[a:a + 3] = dinv[a:a + 3].mean(); dinv[a + 3:a + 6] = dinv[a + 3:a + 6].mean()
-    arrays["dof_invweight0"][:] = dinv
-    # dofs >= ndense never couple to another dof in M (e.g. a free box with its COM at the body origin):
-    # the cooperative Cholesky skips their off-diagonal updates when factoring M and M + h B
-    rs = np.random.default_rng(0)
-    dense = 0
-    for _ in range(4):
-        qr = q0.copy()
-        qr[:len(acts)] += rs.uniform(-0.3, 0.3, len(acts))
-        for l in range(1, nlink):
-            if link_free[l]:
-                a = link_qposadr[l]
-                qr[a + 3:a + 7] = quat_normalize(rs.normal(size=4))
-        Mr = mass_matrix(model, qr)
-        off = np.abs(Mr - np.diag(np.diag(Mr))) > 1e-12
-        idx = np.where(off.any(axis=0))[0]
-        dense = max(dense, int(idx.max()) + 1 if idx.size else 0)
-    sizes[SZ_NDENSE] = dense
-    xpos, xquat = link_kinematics(model, q0)
-    ang, lin, anchor = dof_motion(model, xpos, xquat, q0)
-    body_invw = np.zeros((nb, 2))
-    for i in range(1, nb):
-        l = body_link[i]
-        if l == 0:
-            continue
-        Rl = quat_to_mat(xquat[l])
-        c = xpos[l] + Rl @ (body_lpos[i] + quat_to_mat(body_lquat[i]) @ body_com[i])
-        jp, jr = point_jacobian(model, ang, lin, anchor, l, c)
-        body_invw[i, 0] = np.trace(jp @ Minv @ jp.T) / 3.0
-        body_invw[i, 1] = np.trace(jr @ Minv @ jr.T) / 3.0
-    for k, g in enumerate(g_rec):
-        arrays["geom_invweight"][k] = body_invw[g["body"]]
-    meta["body_invweight0"] = body_invw.tolist()
-    meta["link_mass"] = link_mass.tolist()
+    fill_qpos0_statistics(model, inertials)
     return model
 
 
@@ -966,17 +872,11 @@ TEST_CONFIGS = {
     "meshrest1": dict(dofs=[], n_blocks=1, block_geom=dict(type="mesh", mesh="head_pan"), plane_convex_points=1,
                       block_pos=np.array([[1.0, 0.6, 0.05]])),
 }
-MODEL_DIR = Path(__file__).parent / "models"
-
-
-def load_config(name: str) -> Model:
-    """Load a committed blob (no reference tree needed)."""
-    return Model.load(MODEL_DIR / f"{name}.hsrm")
 
 
 def emit_mjcf(outdir, name: str, dofs: Sequence[str] = ("slide_x", "slide_y"), n_blocks: int = 0,
               block_pos: Optional[np.ndarray] = None, xml_file: str = "models/world.xml",
-              ref_root: Path = DEFAULT_REF_ROOT, set_xml: Sequence = ()) -> Path:
+              ref_root: Path = DEFAULT_REF_ROOT, set_xml: Sequence = (), block_geom: Optional[dict] = None) -> Path:
     """Write the MJCF that the reference's launcher would hand to mujoco-py for this configuration - the mutations of
     hsr/util.py:93-159 (block injection, --set-xml, actuator / joint filter, include and meshdir paths) applied to the
     main file and to every included file - as <outdir>/<name>.xml (+ <name>__<include>).  Anyone with a MuJoCo install
@@ -984,8 +884,7 @@ def emit_mjcf(outdir, name: str, dofs: Sequence[str] = ("slide_x", "slide_y"), n
     ref_root, outdir = Path(ref_root), Path(outdir)
     outdir.mkdir(parents=True, exist_ok=True)
     xml_path = ref_root / xml_file
-    if block_pos is None:
-        block_pos = np.array([[0.0, 0.12 * (i - (n_blocks - 1) / 2.0), 0.422] for i in range(n_blocks)]).reshape(n_blocks, 3)
+    block_pos = _block_positions(block_pos, n_blocks)
     set_xml = [(str(p), str(v)) for p, v in set_xml]
     includes = [e.get("file") for e in ET.parse(xml_path).findall("*/include")]
     out_main = outdir / f"{name}.xml"
@@ -995,20 +894,9 @@ def emit_mjcf(outdir, name: str, dofs: Sequence[str] = ("slide_x", "slide_y"), n
         root = tree.getroot()
         worldbody = root.find("./worldbody")
         if worldbody is not None:
-            for i in range(n_blocks):
-                body = ET.SubElement(worldbody, "body", attrib=dict(name=f"block{i}", pos=" ".join(repr(float(x)) for x in block_pos[i])))
-                ET.SubElement(body, "geom", attrib=dict(name=f"block{i}", type="box", mass="1", size=".05 .025 .017", condim="6",
-                                                        solimp="0.99 0.99 0.01", solref="0.01 1"))
-                ET.SubElement(body, "freejoint", attrib=dict(name=f"block{i}joint"))
+            _inject_blocks(worldbody, block_pos, block_geom)
         _apply_setters(root, set_xml)
-        for acts in root.iter("actuator"):
-            for a in list(acts):
-                if a.get("joint") not in dofs:
-                    acts.remove(a)
-        for body in root.iter("body"):
-            for j in body.findall("joint"):
-                if j.get("name") not in dofs:
-                    body.remove(j)
+        _filter_dofs(root, dofs)
         for inc in root.findall("*/include"):
             inc.set("file", f"{name}__{Path(inc.get('file')).name}")
         for comp in root.findall("compiler"):
@@ -1026,7 +914,7 @@ def main():
     every = dict(CONFIGS, **TEST_CONFIGS)
     if args.emit_mjcf:
         for name, kw in every.items():
-            print(emit_mjcf(args.emit_mjcf, name, **kw))
+            print(emit_mjcf(args.emit_mjcf, name, **{k: v for k, v in kw.items() if k != "plane_convex_points"}))  # not an XML property
         return
     MODEL_DIR.mkdir(exist_ok=True)
     for name, kw in every.items():

@@ -17,7 +17,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from .compiler import Model, load_config
+from .model import Model, load_config
 from .spaces import Box, Space
 
 GoalSpec = namedtuple("GoalSpec", "a b distance")     # hsr/env.py:20

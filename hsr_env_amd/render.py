@@ -16,7 +16,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .compiler import Model, link_kinematics, load_config, quat_to_mat
+from .model import Model, link_kinematics, load_config, quat_to_mat
 
 DEFAULT_SIZE = 500                        # hsr/mujoco_env.py:17
 

@@ -12,7 +12,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .compiler import Model
+from .model import Model
 
 _HERE = Path(__file__).parent
 import os

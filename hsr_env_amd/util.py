@@ -11,8 +11,9 @@ from pathlib import Path
 
 import numpy as np
 
-from .compiler import ALL_DOFS, CONFIGS, DEFAULT_REF_ROOT, compile_model, load_config
+from .compiler import ALL_DOFS, CONFIGS, DEFAULT_REF_ROOT, compile_model
 from .env import GoalSpec
+from .model import load_config
 from .spaces import Box
 
 

@@ -64,11 +64,18 @@ def test_pair_filters(models):
     assert (m.geom_type[m.pair_geom1] <= m.geom_type[m.pair_geom2]).all()
 
 
-@pytest.mark.parametrize("cfg", ["cfg1", "cfg3"])
+@pytest.mark.parametrize("cfg", list(hc.CONFIGS) + list(hc.TEST_CONFIGS))
 def test_recompile_matches_committed_blob(models, cfg):
-    fresh = hc.compile_model(**hc.CONFIGS[cfg], ref_root=REF_DATA)
+    """Every committed blob is what today's compiler makes of the stored data files: arrays (np.linalg.inv need not be bit-stable
+    across machines, hence a tolerance), names, and meta as JSON stores it.  The older blobs predate the plane_convex_points key."""
+    import json
+    fresh = hc.compile_model(**dict(hc.CONFIGS, **hc.TEST_CONFIGS)[cfg], ref_root=REF_DATA)
+    assert set(fresh.arrays) == set(models[cfg].arrays)
     for k, a in models[cfg].arrays.items():
-        assert np.allclose(a, fresh.arrays[k], rtol=1e-12, atol=1e-14), k
+        assert a.shape == fresh.arrays[k].shape and np.allclose(a, fresh.arrays[k], rtol=1e-12, atol=1e-14), k
+    assert fresh.names == models[cfg].names
+    meta = [{k: v for k, v in m.items() if k != "plane_convex_points"} for m in (json.loads(json.dumps(fresh.meta)), models[cfg].meta)]
+    assert meta[0] == meta[1]
 
 
 def test_numpy_mass_matrix_is_spd(models):
