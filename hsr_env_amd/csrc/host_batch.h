@@ -83,6 +83,11 @@ struct hsr_batch {
     float *d_cap = nullptr;        // [rows][12 nlink][cap_n]: the frames of the last step, its final poses in the last row
     size_t cap_floats = 0;
     int cap_rows = 0;              // rows of the last step (frames of its longest possible run + the final one); 0: none since the last set_capture
+    // episodes on the device (hsr_batch_set_episodes, host_episode.h): the spec's tables and the per-env books, allocated by the first call
+    EpisodeDev ep{};
+    bool ep_set = false;           // hsr_batch_set_episodes succeeded at least once: the episode entry points may run
+    float *d_ep_range = nullptr;   // [2 nq]: qpos_lo | qpos_hi
+    int *d_ep_block_qadr = nullptr;     // [free bodies of the model]
 };
 template <typename T>
 static int dalloc(hsr_batch *b, T **p, size_t count) {

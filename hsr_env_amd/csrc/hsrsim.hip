@@ -26,6 +26,7 @@
 #include "solve_mf.h"
 #include "persist.h"
 #include "render.h"
+#include "episode.h"
 #include "cfg_consts.h"
 
 #include "host_model.h"      // error message, blob loader, hsr_model_*, hull planes: plain C++, no HIP
@@ -33,5 +34,6 @@
 #include "util_kernels.h"    // layout / IO / reset / observation / capture kernels, k_queue_init, k_schedule
 #include "host_create.h"     // environment switches, kernel-instance table, plan_persist, model upload, hsr_batch_create / destroy
 #include "host_step.h"       // launch_substep, forward, reset, the persistent launch plan, hsr_batch_step*
+#include "host_episode.h"   // episodes on the device: spec upload, sampled reset, episode end, action sampling (kernels: episode.h)
 #include "host_access.h"     // settings, state / field getters and setters, diagnostics
 #include "host_render.h"     // ray-caster front end and in-step frame capture

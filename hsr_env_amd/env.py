@@ -46,7 +46,8 @@ class VecHSREnv:
                  record_freq: int = None, render_freq: int = None, record_path: Path = None,
                  n_envs: int = 1, model: Optional[Model] = None, sim=None, device: int = 0,
                  env_offset: int = 0, n_global: Optional[int] = None, block_space: Optional[Box] = None,
-                 record_envs: Optional[List[int]] = None, record_size=None, record_camera=None):
+                 record_envs: Optional[List[int]] = None, record_size=None, record_camera=None,
+                 auto_reset: bool = False, max_episode_steps: Optional[int] = None):
         if model is None:
             model = load_config(str(xml_file)) if xml_file is not None else None
         if model is None:
@@ -76,9 +77,21 @@ class VecHSREnv:
         self._block_name = model.block_body() or "block0"
         self._finger_names = ["hand_l_distal_link", "hand_r_distal_link"]
         if sim is None:
+            if auto_reset:
+                import torch  # noqa: F401  the device loop's buffers are torch tensors, and torch's HIP runtime must be the first one
+                #                            loaded into the process: after the library's, torch finds no GPU
             from .sim import BatchSim
             sim = BatchSim(model, self.n_envs, device=device)
         self.sim = sim
+        # episodes on the device (episodes.py, csrc/episode.h): reset states, goals and the time limit are drawn and kept by the batch,
+        # and step() resets the envs that finished.  Opt-in; the host-sampled reset below stays what it is.  No CPU stand-in.
+        self.auto_reset = bool(auto_reset)
+        self.max_episode_steps = int(max_episode_steps or 0)
+        if max_episode_steps is not None and not self.auto_reset:
+            raise ValueError("max_episode_steps belongs to auto_reset=True (rl.TimeLimit wraps an env without it)")
+        if self.auto_reset and not hasattr(sim, "set_episodes"):
+            raise NotImplementedError("auto_reset=True needs a simulator handle with set_episodes (BatchSim): episodes run on the device")
+        self._dev = None
         # hsr/env.py:50-66: record when any of record / record_path / record_freq is given.  One video per recorded env (global ids
         # record_envs, default [0]; a rank records the ones in its shard) under the directory record_path (record.py)
         self._recorder = None
@@ -152,6 +165,11 @@ class VecHSREnv:
         self._seed = 0 if seed is None else int(seed)
         self._reset_count = 0
         self.np_random = np.random.Generator(np.random.Philox(key=self._seed))
+        if self.auto_reset:                                             # the device sampler restarts: same seed, same run
+            from .episodes import EpisodeSpec
+            self.sim.set_episodes(EpisodeSpec.from_env(self.model, self.starts, self.goals_specs, self.block_space, seed=self._seed,
+                                                       env_offset=self.env_offset, max_episode_steps=self.max_episode_steps))
+            self._action_step = 0
         return [seed]
 
     def _global_rng(self):
@@ -181,6 +199,8 @@ class VecHSREnv:
 
     def reset(self, mask=None):
         """sim.reset() + reset_model() (hsr/mujoco_env.py:83-85, hsr/env.py:158-177); ``mask`` selects envs."""
+        if self.auto_reset:
+            return self._reset_sampled(mask)
         rng = self._global_rng()
         self._reset_count += 1
         m = np.ones(self.n_envs, dtype=bool) if mask is None else np.asarray(mask, dtype=bool).reshape(self.n_envs)
@@ -203,6 +223,104 @@ class VecHSREnv:
         self.sim.reset(mask=m.astype(np.uint8), qpos0=qpos, mocap=self._goal_points)
         return self._get_observation()
 
+    # ------------------------------------------------------------------ episodes on the device (auto_reset=True)
+    def _begin_goals(self):
+        if self.goals_specs:
+            if self._extra_terms and self.goals is None:
+                self.sim.set_goals(self._extra_terms)
+            if self.goals is None:
+                self.goals = list(self.goals_specs)
+
+    def _refresh_goal_points(self):
+        """The goal points the device drew (its mocap_pos) -> ``goals`` / ``in_range``."""
+        if self._point_goal is None or self.goals is None:
+            return
+        mocap_body = next(i for i, mc in enumerate(self.model.arrays["body_mocap"]) if mc)
+        self._goal_points = np.asarray(self.sim.body_xpos(mocap_body), dtype=np.float32)
+        a, b, d = self.goals_specs[self._point_goal]
+        cur = self._squeeze(self._goal_points)
+        self.goals[self._point_goal] = GoalSpec(a, cur, d) if isinstance(a, str) else GoalSpec(cur, b, d)
+
+    def _reset_sampled(self, mask):
+        m = np.ones(self.n_envs, dtype=bool) if mask is None else np.asarray(mask, dtype=bool).reshape(self.n_envs)
+        if self._recorder is not None:
+            self._recorder.on_reset(m, self._time_steps > 0)
+        self._time_steps[m] = 0
+        self._begin_goals()
+        self.sim.reset_sampled(m)
+        self._refresh_goal_points()
+        return self._get_observation()
+
+    def _device_buffers(self):
+        """torch tensors on the batch's device and the batch's stream as a torch stream: what the device loop reads and writes."""
+        if self._dev is None:
+            import torch
+            dev = torch.device("cuda", getattr(self.sim, "device", 0))
+            n, no = self.n_envs, self.model.nq + self.model.nv
+            f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+            self._dev = dict(stream=torch.cuda.ExternalStream(self.sim.stream_ptr(), device=dev), ctrl=f32(n, self.model.nu), obs=f32(n, no),
+                             final=f32(n, no), rew=f32(n), fret=f32(n), done=torch.zeros(n, dtype=torch.uint8, device=dev),
+                             kind=torch.zeros(n, dtype=torch.uint8, device=dev), ns=torch.zeros(n, dtype=torch.int32, device=dev),
+                             flen=torch.zeros(n, dtype=torch.int32, device=dev))
+            torch.cuda.synchronize(dev)                                 # the fills ran on torch's stream, the batch has its own
+        return self._dev
+
+    def sample_action_dev(self):
+        """Uniform actions over the action space drawn on the device (torch float32 [n_envs, nu]); every call is the next action step."""
+        import torch
+        d = self._device_buffers()
+        with torch.cuda.stream(d["stream"]):
+            self.sim.sample_ctrl_dev(self._action_step, d["ctrl"].data_ptr())
+        self._action_step += 1
+        return d["ctrl"]
+
+    def _step_auto_reset(self, action, steps):
+        import torch
+        d = self._device_buffers()
+        goal_body = self._goal_body if self.goals else -1
+        with torch.cuda.stream(d["stream"]):
+            if isinstance(action, torch.Tensor):
+                if action.data_ptr() != d["ctrl"].data_ptr():
+                    d["ctrl"].copy_(action.reshape(self.n_envs, self.model.nu))
+            else:
+                d["ctrl"].copy_(torch.from_numpy(np.ascontiguousarray(action, dtype=np.float32).reshape(self.n_envs, self.model.nu)))
+            ptr = {k: v.data_ptr() for k, v in d.items() if k != "stream"}
+            self.sim.step_dev(ptr["ctrl"], steps, goal_body, self._geofence, ptr["obs"], ptr["rew"], ptr["done"], ptr["ns"])
+            bad, any_bad = self.sim.bad_state()
+            if any_bad:
+                from .sim import MujocoException
+                raise MujocoException(f"simulation diverged in env(s) {np.flatnonzero(bad)[:8].tolist()} (non-finite or |q| > 1e10)")
+            self._time_steps += 1
+            if self._recorder is not None:
+                self._recorder.after_step(d["done"].cpu().numpy().astype(bool), d["ns"].cpu().numpy())
+            final = self.sim.obs_openai() if self._obs_type == "openai" else None       # before the reset moves the bodies
+            self.sim.episode_end_dev(ptr["obs"], ptr["rew"], ptr["done"], ptr["final"] if final is None else None, ptr["kind"], ptr["fret"], ptr["flen"])
+            host = {k: d[k].cpu().numpy() for k in ("obs", "rew", "done", "ns", "kind", "fret", "flen")}
+            if final is None:
+                final = d["final"].cpu().numpy()
+        kind = host["kind"]
+        reset = kind != 0
+        if self._recorder is not None:
+            self._recorder.on_reset(reset, self._time_steps > 0)
+        success = host["done"].astype(bool)
+        info = {"log count": {"success": self._squeeze(success & (self._time_steps > 0))}, "substeps": self._squeeze(host["ns"]),
+                "terminal_observation": self._squeeze(final), "TimeLimit.truncated": self._squeeze(kind == 2),
+                "episode": {"r": self._squeeze(host["fret"]), "l": self._squeeze(host["flen"])}}
+        self._time_steps[reset] = 0
+        obs = host["obs"]
+        if reset.any():
+            self._refresh_goal_points()
+            if self._obs_type == "openai":
+                obs = self.sim.obs_openai()
+        elif self._obs_type == "openai":
+            obs = final
+        self._last_obs = obs
+        if self.n_envs == 1:
+            info["TimeLimit.truncated"] = bool(kind[0] == 2)
+            info["episode"] = {"r": float(host["fret"][0]), "l": int(host["flen"][0])}
+            return obs[0], float(host["rew"][0]), bool(reset[0]), info
+        return obs, host["rew"], reset, info
+
     def set_state(self, qpos, qvel):
         qpos = np.asarray(qpos, dtype=np.float32).reshape(self.n_envs, -1)
         qvel = np.asarray(qvel, dtype=np.float32).reshape(self.n_envs, -1)
@@ -222,9 +340,14 @@ class VecHSREnv:
         return self._squeeze(self._last_obs)
 
     def step(self, action, steps=None):
-        """hsr/env.py:115-135 for every env: returns (obs, reward, done, info)."""
-        action = np.asarray(action, dtype=np.float32).reshape(self.n_envs, self.model.nu)
+        """hsr/env.py:115-135 for every env: returns (obs, reward, done, info).  With auto_reset=True the envs that are done or out of
+        time are reset inside the call: done = done | truncated, info['terminal_observation'] is what the step itself produced,
+        info['TimeLimit.truncated'] and info['episode'] = {'r', 'l'} (valid where done) describe the episode that ended, and the
+        returned rows of those envs are the first observation of their next episode.  `action` may then be a torch tensor on the device."""
         steps = steps or self.steps_per_action
+        if self.auto_reset:
+            return self._step_auto_reset(action, steps)
+        action = np.asarray(action, dtype=np.float32).reshape(self.n_envs, self.model.nu)
         goal_body = self._goal_body if self.goals else -1
 
         obs, rew, done, ns = self.sim.step(action, steps, goal_body, self._geofence)

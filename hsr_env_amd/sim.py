@@ -88,6 +88,12 @@ PROTOTYPES = {
     "hsr_batch_cap_histogram": (_int, [_vp, _ullp]),
     "hsr_batch_newton_trips": (_int, [_vp, _i32p]),
     "hsr_batch_packing": (_int, [_vp, _i32p]),
+    "hsr_batch_set_episodes": (_int, [_vp, _vp]),
+    "hsr_batch_reset_sampled_dev": (_int, [_vp, _vp]),
+    "hsr_batch_reset_sampled": (_int, [_vp, _u8p]),
+    "hsr_batch_episode_end_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hsr_batch_sample_ctrl_dev": (_int, [_vp, C.c_uint32, _vp]),
+    "hsr_batch_episode_state": (_int, [_vp, C.POINTER(C.c_uint32), _i32p, _fp_t]),
     "hsr_batch_phase_cycles": (_int, [_vp, _ullp]),
     "hsr_batch_block_times": (_int, [_vp, _ullp, _int]),
 }
@@ -183,6 +189,38 @@ class BatchSim:
 
     def forward(self):
         _check(self._L, self._L.hsr_batch_forward(self._b))
+
+    # -- episodes on the device (include/hsrsim.h: hsr_batch_set_episodes ..; episodes.EpisodeSpec builds the spec)
+    def set_episodes(self, spec):
+        """Upload the sampler's tables and zero the per-env books (episode index, length, return); synchronises."""
+        c, keep = spec.to_c()
+        _check(self._L, self._L.hsr_batch_set_episodes(self._b, C.byref(c)))
+        del keep
+
+    def reset_sampled(self, mask=None):
+        """The masked envs (all if None) draw their next episode on the device and restart from it; synchronises."""
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask).reshape(self.n) != 0, dtype=np.uint8)
+        _check(self._L, self._L.hsr_batch_reset_sampled(self._b, None if m is None else m.ctypes.data_as(_u8p)))
+
+    def reset_sampled_dev(self, d_mask=None):
+        """reset_sampled with a device mask (uint8 [N] pointer; None: all envs); asynchronous on the batch stream."""
+        _check(self._L, self._L.hsr_batch_reset_sampled_dev(self._b, d_mask))
+
+    def episode_end_dev(self, d_obs, d_reward, d_done, d_final_obs=None, d_reset_kind=None, d_fin_return=None, d_fin_length=None):
+        """Close the env-step step_dev just ran: books, time limit, sampled reset of the envs that are done or truncated (device
+        pointers: float32 [N,nq+nv], float32 [N], uint8 [N]; outputs float32 [N,nq+nv], uint8 [N] (0 / 1 done / 2 truncated),
+        float32 [N], int32 [N], any None); asynchronous on the batch stream."""
+        _check(self._L, self._L.hsr_batch_episode_end_dev(self._b, d_obs, d_reward, d_done, d_final_obs, d_reset_kind, d_fin_return, d_fin_length))
+
+    def sample_ctrl_dev(self, step: int, d_ctrl):
+        """d_ctrl float32 [N,nu] ~ U(ctrlrange) for action step `step` (0 .. 2**32 - 1); asynchronous on the batch stream."""
+        _check(self._L, self._L.hsr_batch_sample_ctrl_dev(self._b, int(step) & 0xffffffff, d_ctrl))
+
+    def episode_state(self):
+        """(episode index uint32 [N], length int32 [N], return float32 [N]) of every env; synchronises."""
+        i = np.empty(self.n, np.uint32); l = np.empty(self.n, np.int32); r = np.empty(self.n, np.float32)
+        _check(self._L, self._L.hsr_batch_episode_state(self._b, i.ctypes.data_as(C.POINTER(C.c_uint32)), l.ctypes.data_as(_i32p), _fp(r)))
+        return i, l, r
 
     def get_state(self):
         t = np.empty(self.n, np.float32); q = np.empty((self.n, self.nq), np.float32); v = np.empty((self.n, self.nv), np.float32)

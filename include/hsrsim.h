@@ -223,6 +223,51 @@ int hsr_batch_newton_trips(hsr_batch *b, int32_t *out /*[n_envs]*/);
  * filled from the easy end.  Results never depend on it. */
 int hsr_batch_packing(hsr_batch *b, int32_t *out /*[ceil(n_envs / epw) * epw]*/);
 
+/* ---- episodes on the device: sampled auto-reset, time limit, episode statistics -------------------------------------------------
+ * Opt-in.  hsr_batch_reset / hsr_batch_reset_dev above know nothing of episodes: they neither sample nor touch the books below.
+ *
+ * Draws come from Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter = (gid, episode, stream, block) with
+ * gid = env_offset + e, so a shard at env_offset draws what the single batch draws for the same envs.  A 32-bit word x gives
+ * u = (x >> 8) 2^-24 and the value min(hi, lo + u (hi - lo)), every operation rounded to float32 on its own; lo == hi gives lo.
+ *   stream 0: qpos[i] = word i % 4 of block i / 4 over (qpos_lo[i], qpos_hi[i])
+ *   stream 1: the goal point (mocap_pos) = words 0..2 of block 0 over (goal_lo, goal_hi); has_goal == 0: the point is 0
+ *   stream 2: the pose of block k = words 0..3 of block k: x, y, z, yaw over (block_lo, block_hi), written to qpos[block_qadr[k] ..+7) as
+ *             (x, y, z, cos(yaw/2), 0, 0, sin(yaw/2)) in place of what stream 0 drew there
+ *   stream 3: ctrl[a] = word a % 4 of block a / 4 over the actuator's ctrlrange; the second counter word is the caller's action step */
+typedef struct hsr_episode_spec {
+    uint64_t seed;
+    uint32_t env_offset;           /* global id of the batch's env 0 */
+    int32_t max_episode_steps;     /* env-steps after which an episode is truncated; 0 = no limit */
+    const float *qpos_lo, *qpos_hi; /* [nq]; lo == hi == qpos0 where nothing is sampled */
+    int32_t has_goal;
+    float goal_lo[3], goal_hi[3];
+    int32_t nblock;                /* free bodies placed by stream 2 (0: none) */
+    const int32_t *block_qadr;     /* [nblock] qpos address of each one's free joint */
+    float block_lo[4], block_hi[4]; /* x, y, z, yaw */
+} hsr_episode_spec;
+/* uploads the spec, allocates (first call) and zeroes the per-env books: episode index, length and return.  Synchronises.
+ * HSR_EINVAL: a NULL spec or table, a bound that is not finite, lo > hi, max_episode_steps < 0, nblock above the model's free bodies, a
+ * block_qadr that is not the address of a free joint.  A refused call leaves the batch as it was. */
+int hsr_batch_set_episodes(hsr_batch *b, const hsr_episode_spec *spec);
+/* the envs with d_mask[e] != 0 (all if NULL) draw episode ep_index[e], restart from it as in hsr_batch_reset_dev (state reset, forward),
+ * ep_index[e] += 1, length and return <- 0.  The dev variant is asynchronous; the host-mask twin synchronises. */
+int hsr_batch_reset_sampled_dev(hsr_batch *b, const uint8_t *d_mask);
+int hsr_batch_reset_sampled(hsr_batch *b, const uint8_t *mask);
+/* Closes the env-step hsr_batch_step_dev just ran, asynchronous on hsr_batch_stream().  Per env: return += reward, length += 1;
+ * truncated = max_episode_steps > 0 and length >= max_episode_steps; reset kind = done ? 1 : truncated ? 2 : 0.  Envs of kind 1 / 2 publish
+ * return and length in d_fin_return / d_fin_length (0 for the others), draw their next episode and restart from it exactly as
+ * hsr_batch_reset_dev(mask, ...) would: the other envs keep every bit of their state.  d_final_obs receives d_obs as the step left it;
+ * then the d_obs rows of the reset envs become the new episode's first observation, concat(qpos, 0).
+ * d_obs / d_reward / d_done are what the step wrote (NULL: obs is not touched; reward = done; done = the flag the step latched);
+ * every output may be NULL.  HSR_EINVAL before hsr_batch_set_episodes. */
+int hsr_batch_episode_end_dev(hsr_batch *b, float *d_obs, const float *d_reward, const uint8_t *d_done, float *d_final_obs,
+                              uint8_t *d_reset_kind, float *d_fin_return, int32_t *d_fin_length);
+/* d_ctrl[N,nu] ~ U(ctrlrange) from stream 3 for action step `step`; a side without a limit (not finite, or the compiled models' marker
+ * 1e30) counts as -1 / +1.  Asynchronous. */
+int hsr_batch_sample_ctrl_dev(hsr_batch *b, uint32_t step, float *d_ctrl);
+/* host copies of the books (any may be NULL); synchronises */
+int hsr_batch_episode_state(hsr_batch *b, uint32_t *ep_index, int32_t *ep_length, float *ep_return);
+
 /* diagnostics (meaningful only in the -DHSR_PHASE_TIMING build, libhsrsim_timing.so; tools/phase_timing.py,
  * tools/block_times.py): per-phase cycle sums of the last launches, and per-workgroup
  * {start, end (s_memrealtime), HW_ID, XCC_ID, Newton trips, sphere-cull candidates, work items, rows} */
