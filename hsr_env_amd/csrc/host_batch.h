@@ -88,7 +88,15 @@ struct hsr_batch {
     bool ep_set = false;           // hsr_batch_set_episodes succeeded at least once: the episode entry points may run
     float *d_ep_range = nullptr;   // [2 nq]: qpos_lo | qpos_hi
     int *d_ep_block_qadr = nullptr;     // [free bodies of the model]
+    // snapshots (host_snapshot.h): the ones this batch made and nobody destroyed yet - hsr_batch_destroy releases their storage -, and the
+    // scratch one hsr_batch_copy_envs* goes through, made by its first call (one of `snapshots`, so its storage goes the same way);
+    // the record's descriptor table (snapshot.h), built by the first launch that needs it
+    std::vector<hsr_snapshot *> snapshots;
+    hsr_snapshot *fork_scratch = nullptr;
+    SnapTable snap_tab{};
+    bool snap_tab_built = false;   // snap_table checks the episode books' pointers in it against the batch's on every use
 };
+static void snap_release_all(hsr_batch *b);     // host_snapshot.h
 template <typename T>
 static int dalloc(hsr_batch *b, T **p, size_t count) {
     void *q = nullptr;

@@ -30,6 +30,7 @@ struct hsr_model {
     std::map<std::string, const BlobEntry *> entries;
     const uint8_t *data = nullptr;
     std::string json;
+    uint64_t fingerprint = 0;      // 64-bit FNV-1a of the blob's bytes: what a snapshot is bound to (host_snapshot.h)
     int sizes[16];
     double opt[16];
     std::vector<std::string> body_names, joint_names;
@@ -119,6 +120,8 @@ extern "C" int hsr_model_load(const void *blob, size_t len, hsr_model **out) {
     hsr_model *m = new hsr_model();
     m->raw.assign(in, in + len);
     const uint8_t *raw = m->raw.data();
+    m->fingerprint = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < len; i++) m->fingerprint = (m->fingerprint ^ raw[i]) * 0x100000001b3ull;
     const BlobEntry *ent = (const BlobEntry *)(raw + 16);
     const uint8_t *p = raw + 16 + (size_t)n * sizeof(BlobEntry);
     m->json.assign((const char *)p + 8, (size_t)jl);

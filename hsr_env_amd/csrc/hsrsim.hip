@@ -27,6 +27,7 @@
 #include "persist.h"
 #include "render.h"
 #include "episode.h"
+#include "snapshot.h"
 #include "cfg_consts.h"
 
 #include "host_model.h"      // error message, blob loader, hsr_model_*, hull planes: plain C++, no HIP
@@ -37,3 +38,4 @@
 #include "host_episode.h"   // episodes on the device: spec upload, sampled reset, episode end, action sampling (kernels: episode.h)
 #include "host_access.h"     // settings, state / field getters and setters, diagnostics
 #include "host_render.h"     // ray-caster front end and in-step frame capture
+#include "host_snapshot.h"   // env records on the device: save / load / env-to-env copy, the host image (kernel: snapshot.h)

@@ -21,6 +21,8 @@ from .model import Model, load_config
 from .spaces import Box, Space
 
 GoalSpec = namedtuple("GoalSpec", "a b distance")     # hsr/env.py:20
+# what VecHSREnv.save_state returns: the device records of every env (sim.Snapshot) and the host books that belong to them
+EnvState = namedtuple("EnvState", "snapshot time_steps goal_points reset_count action_step last_obs began")
 
 
 def distance_between(pos1, pos2):                        # hsr/env.py:231-232
@@ -237,6 +239,12 @@ class VecHSREnv:
             return
         mocap_body = next(i for i, mc in enumerate(self.model.arrays["body_mocap"]) if mc)
         self._goal_points = np.asarray(self.sim.body_xpos(mocap_body), dtype=np.float32)
+        self._publish_goal_points()
+
+    def _publish_goal_points(self):
+        """``goals`` holds the point goal with the current ``_goal_points``."""
+        if self._point_goal is None or self.goals is None:
+            return
         a, b, d = self.goals_specs[self._point_goal]
         cur = self._squeeze(self._goal_points)
         self.goals[self._point_goal] = GoalSpec(a, cur, d) if isinstance(a, str) else GoalSpec(cur, b, d)
@@ -320,6 +328,46 @@ class VecHSREnv:
             info["episode"] = {"r": float(host["fret"][0]), "l": int(host["flen"][0])}
             return obs[0], float(host["rew"][0]), bool(reset[0]), info
         return obs, host["rew"], reset, info
+
+    # ------------------------------------------------------------------ exact snapshots (sim.Snapshot)
+    def _no_jump_while_recording(self, what):
+        if self._recorder is not None:
+            raise NotImplementedError(f"{what} while a recorder is attached: a video cannot jump")
+
+    def save_state(self) -> EnvState:
+        """sim.get_state() in its exact form (hsr/env.py:69,150; hsr/mujoco_env.py:87-94): every env's device record - state, warm start,
+        collision caches, poses, episode books - and this object's own books.  load_state() of it continues bit for bit."""
+        self._no_jump_while_recording("save_state")
+        snap = self.sim.snapshot()
+        snap.save()
+        return EnvState(snap, self._time_steps.copy(), self._goal_points.copy(), self._reset_count, getattr(self, "_action_step", 0),
+                        self._last_obs.copy(), self.goals is not None)
+
+    def load_state(self, state: EnvState):
+        """sim.set_state() in its exact form (hsr/env.py:175; hsr/mujoco_env.py:87-94): no forward pass, nothing recomputed."""
+        self._no_jump_while_recording("load_state")
+        if state.began != (self.goals is not None):
+            raise ValueError("load_state: the state was saved on the other side of the first reset()")
+        state.snapshot.load(into=self.sim)
+        self._time_steps[:] = state.time_steps
+        self._goal_points = state.goal_points.copy()
+        self._reset_count = state.reset_count
+        if self.auto_reset:
+            self._action_step = state.action_step
+        self._last_obs = state.last_obs.copy()
+        self._publish_goal_points()
+
+    def fork(self, src, dst):
+        """Envs `dst` become copies of env(s) `src` (one id for all, or one per destination), on the device, and continue bit for bit as
+        their sources do; with auto_reset=True their next episodes are drawn with their own env ids."""
+        self._no_jump_while_recording("fork")
+        dst = np.atleast_1d(np.asarray(dst, dtype=np.int32))
+        src = np.broadcast_to(np.asarray(src, dtype=np.int32), dst.shape).copy()
+        self.sim.copy_envs(src, dst)
+        self._time_steps[dst] = self._time_steps[src]
+        self._goal_points[dst] = self._goal_points[src]
+        self._last_obs[dst] = self._last_obs[src]
+        self._publish_goal_points()
 
     def set_state(self, qpos, qvel):
         qpos = np.asarray(qpos, dtype=np.float32).reshape(self.n_envs, -1)

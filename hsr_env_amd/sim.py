@@ -96,6 +96,20 @@ PROTOTYPES = {
     "hsr_batch_episode_state": (_int, [_vp, C.POINTER(C.c_uint32), _i32p, _fp_t]),
     "hsr_batch_phase_cycles": (_int, [_vp, _ullp]),
     "hsr_batch_block_times": (_int, [_vp, _ullp, _int]),
+    "hsr_batch_snapshot_create": (_int, [_vp, _int, C.POINTER(_vp)]),
+    "hsr_snapshot_destroy": (None, [_vp]),
+    "hsr_snapshot_capacity": (_int, [_vp]),
+    "hsr_batch_snapshot_save": (_int, [_vp, _vp, _i32p, _i32p, _int]),
+    "hsr_batch_snapshot_save_dev": (_int, [_vp, _vp, _vp, _vp, _int]),
+    "hsr_batch_snapshot_load": (_int, [_vp, _vp, _i32p, _i32p, _int]),
+    "hsr_batch_snapshot_load_dev": (_int, [_vp, _vp, _vp, _vp, _int]),
+    "hsr_batch_copy_envs": (_int, [_vp, _i32p, _i32p, _int]),
+    "hsr_batch_copy_envs_dev": (_int, [_vp, _vp, _vp, _int]),
+    "hsr_snapshot_image_bytes": (_int, [_vp, C.POINTER(C.c_longlong)]),
+    "hsr_snapshot_export": (_int, [_vp, _vp, C.c_longlong]),
+    "hsr_snapshot_import": (_int, [_vp, C.c_char_p, C.c_longlong]),
+    "hsr_model_snapshot_record_words": (_int, [_vp]),
+    "hsr_model_snapshot_image_check": (_int, [_vp, C.c_char_p, C.c_longlong, _ip]),
 }
 EXPORTS = list(PROTOTYPES)
 
@@ -221,6 +235,20 @@ class BatchSim:
         i = np.empty(self.n, np.uint32); l = np.empty(self.n, np.int32); r = np.empty(self.n, np.float32)
         _check(self._L, self._L.hsr_batch_episode_state(self._b, i.ctypes.data_as(C.POINTER(C.c_uint32)), l.ctypes.data_as(_i32p), _fp(r)))
         return i, l, r
+
+    # -- exact snapshots (include/hsrsim.h: hsr_batch_snapshot_create ..; the class Snapshot below)
+    def snapshot(self, capacity=None) -> "Snapshot":
+        """Device storage for `capacity` env records (default: one per env), bound to this batch's model and device."""
+        return Snapshot(self, self.n if capacity is None else capacity)
+
+    def copy_envs(self, src, dst):
+        """env dst[i] <- env src[i] on the device, every source read before any destination is written; the destinations then continue
+        bit for bit as their sources do.  int32 numpy arrays / sequences (checked, synchronises) or torch int32 tensors on the batch's
+        device (asynchronous on the batch stream; ids out of range are skipped, a repeated destination is the caller's error)."""
+        dev, a, b, n, keep = _id_pair(self, src, dst)
+        fn = self._L.hsr_batch_copy_envs_dev if dev else self._L.hsr_batch_copy_envs
+        _check(self._L, fn(self._b, a, b, n))
+        del keep
 
     def get_state(self):
         t = np.empty(self.n, np.float32); q = np.empty((self.n, self.nq), np.float32); v = np.empty((self.n, self.nv), np.float32)
@@ -491,3 +519,91 @@ class BatchSim:
         tot = C.c_float(0); k = (C.c_float * 3)(); n = (C.c_int * 3)()
         _check(self._L, self._L.hsr_batch_last_timing(self._b, C.byref(tot), k, n))
         return float(tot.value), [float(x) for x in k], [int(x) for x in n]
+
+
+def _id_pair(sim, a, b):
+    """Two id arrays of one length (either may be None = 0..n-1; both None: every env) -> (device variant?, pointer a, pointer b, n, what
+    keeps the pointers alive).  numpy arrays / sequences: int32 host pointers; torch tensors (int32, contiguous, on the batch's device):
+    their data_ptr()."""
+    dev = [x is not None and hasattr(x, "data_ptr") for x in (a, b)]
+    if any(dev):
+        for x in (a, b):
+            if x is None:
+                continue
+            if not hasattr(x, "data_ptr"):
+                raise AssertionError("ids: device tensors and host arrays cannot be mixed in one call")
+            if str(x.dtype) != "torch.int32" or x.dim() != 1 or not x.is_contiguous() or x.device.type != "cuda" or x.device.index != sim.device:
+                raise AssertionError(f"ids: expected a contiguous 1-d torch.int32 tensor on cuda:{sim.device}")
+        ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        keep = (a, b)
+    else:
+        a, b = [None if x is None else np.ascontiguousarray(np.atleast_1d(x), dtype=np.int32) for x in (a, b)]
+        for x in (a, b):
+            if x is not None and x.ndim != 1:
+                raise AssertionError("ids: expected 1-d arrays")
+        ptr = lambda x: None if x is None else x.ctypes.data_as(_i32p)
+        keep = (a, b)
+    lens = {int(x.shape[0]) for x in keep if x is not None}
+    if len(lens) > 1:
+        raise AssertionError("ids: the two arrays differ in length")
+    return any(dev), ptr(keep[0]), ptr(keep[1]), (lens.pop() if lens else sim.n), keep
+
+
+class Snapshot:
+    """Env records on the device (include/hsrsim.h: hsr_snapshot): everything of an env that a later step, forward or getter reads -
+    state, warm start, collision caches, last poses, episode books - so that a loaded env continues bit for bit.  Bound to
+    the model and the device of the batch that made it, not to the batch: ``load(into=other)`` restores into another BatchSim of the
+    same model.  Its storage is released by close() or by close() of the batch that made it, whichever comes first."""
+
+    def __init__(self, sim: BatchSim, capacity: int):
+        self.sim = sim
+        self._s = C.c_void_p()
+        _check(sim._L, sim._L.hsr_batch_snapshot_create(sim._b, int(capacity), C.byref(self._s)))
+        self.capacity = int(capacity)
+
+    def close(self):
+        if getattr(self, "_s", None):
+            self.sim._L.hsr_snapshot_destroy(self._s); self._s = None
+
+    __del__ = close
+
+    def save(self, envs=None, slots=None):
+        """record slots[i] <- env envs[i] (None: 0..n-1; both None: every env, capacity permitting).  Host ids are checked and the call
+        synchronises; torch int32 tensors on the batch's device launch asynchronously on the batch stream."""
+        dev, e, s, n, keep = _id_pair(self.sim, envs, slots)
+        L = self.sim._L
+        _check(L, (L.hsr_batch_snapshot_save_dev if dev else L.hsr_batch_snapshot_save)(self.sim._b, self._s, e, s, n))
+        del keep
+
+    def load(self, slots=None, envs=None, into: BatchSim = None):
+        """env envs[i] <- record slots[i] of `into` (default: the batch that made the snapshot; None: 0..n-1; both None: every env, capacity
+        permitting, as in save()); a slot may feed any number of envs.  No forward pass runs: the loaded envs hold the poses the record was
+        saved with."""
+        sim = into if into is not None else self.sim
+        dev, s, e, n, keep = _id_pair(sim, slots, envs)
+        L = sim._L
+        _check(L, (L.hsr_batch_snapshot_load_dev if dev else L.hsr_batch_snapshot_load)(sim._b, self._s, s, e, n))
+        del keep
+
+    def to_bytes(self) -> bytes:
+        """The host image (header + records): what a checkpoint file holds."""
+        L = self.sim._L
+        size = C.c_longlong(0)
+        _check(L, L.hsr_snapshot_image_bytes(self._s, C.byref(size)))
+        buf = C.create_string_buffer(size.value)
+        _check(L, L.hsr_snapshot_export(self._s, buf, size.value))
+        return buf.raw
+
+    def _from_image(self, data: bytes):
+        """Replace the records by those of an image of the same model and capacity (IOError otherwise; the records then stay as they were)."""
+        L = self.sim._L
+        _check(L, L.hsr_snapshot_import(self._s, bytes(data), len(data)))
+        return self
+
+    @classmethod
+    def from_bytes(cls, sim: BatchSim, data: bytes) -> "Snapshot":
+        """A snapshot of `sim`'s model holding the records of an image written by to_bytes() (IOError: not an image of this model)."""
+        L = sim._L
+        cap = C.c_int(0)
+        _check(L, L.hsr_model_snapshot_image_check(sim._m, bytes(data), len(data), C.byref(cap)))
+        return cls(sim, cap.value)._from_image(data)

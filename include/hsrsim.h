@@ -29,6 +29,7 @@ extern "C" {
 
 typedef struct hsr_model hsr_model;
 typedef struct hsr_batch hsr_batch;
+typedef struct hsr_snapshot hsr_snapshot;
 
 /* indices for hsr_model_size() */
 enum hsr_size { HSR_NQ = 0, HSR_NV, HSR_NU, HSR_NLINK, HSR_NBODY, HSR_NGEOM, HSR_NPAIR, HSR_NMESHVERT,
@@ -267,6 +268,56 @@ int hsr_batch_episode_end_dev(hsr_batch *b, float *d_obs, const float *d_reward,
 int hsr_batch_sample_ctrl_dev(hsr_batch *b, uint32_t step, float *d_ctrl);
 /* host copies of the books (any may be NULL); synchronises */
 int hsr_batch_episode_state(hsr_batch *b, uint32_t *ep_index, int32_t *ep_length, float *ep_return);
+
+/* ---- exact snapshots: save, restore and fork envs on the device, bit for bit -----------------------------------------------------
+ * sim.get_state() / sim.set_state() (hsr/env.py:69,150,175; hsr/mujoco_env.py:87-94) in their exact form.  hsr_batch_set_state above voids
+ * the collision caches and runs a forward pass: the batch it leaves is a cold start.  A snapshot holds env RECORDS: everything of an env
+ * that a later step / forward / getter reads before it writes -
+ *   qpos qvel ctrl mocap_pos qacc_warmstart time, the done / bad-state flags and the substep count of the last step;
+ *   the collision caches (cached separating axes and margins, the MPR portals of penetrating pairs, their stamps and the env's tick);
+ *   the Newton-iteration count that wave packing reads (never changes a result);
+ *   the link poses and velocities of the last forward pass (hsr_batch_body_xpos, _obs_openai, _render and the goal terms read them): a load
+ *   runs no forward pass;
+ *   the episode books (index, length, return): zero in a record saved before hsr_batch_set_episodes, loaded only into a batch that has them;
+ *   an env's next episode is drawn with key (gid of the env it was loaded into, restored episode index).
+ * A loaded env continues bit for bit as the saved one did, in any slot of any batch of the same model (results never depend on either).
+ * NOT in a record: the solver's and the narrowphase's intermediates (for a loaded env hsr_batch_get_field other than HSR_F_XPOS / HSR_F_XMAT
+ * describes nothing until the next forward or step), capture slots and frames, goals, settings, cap statistics.
+ * Records are copied as 32-bit patterns (NaN payloads and -0 survive).  A snapshot is bound to a model (the 64-bit FNV-1a hash of its blob,
+ * computed by hsr_model_load) and a device, not to the batch that made it: it may be loaded into another batch of the same model on the
+ * same device.  Its device storage is released by hsr_snapshot_destroy, or by hsr_batch_destroy of the batch that made it, whichever
+ * comes first: after the latter the handle is still the caller's to destroy, and every other use of it returns HSR_EINVAL.
+ *
+ * Host variants take host id arrays, check everything and synchronise; HSR_EINVAL leaves batch and snapshot untouched: a NULL handle, n < 0
+ * or above the batch's envs or the capacity, an id out of range, a repeated destination (env for load / copy, slot for save), capacity < 1,
+ * a snapshot of another model or device.  The _dev variants take device id arrays and are asynchronous on hsr_batch_stream(); they check
+ * what the host can see (handles, n, model, device); ids out of range are skipped (nothing is read or written for them); repeated
+ * destinations are the caller's error - which source wins is unspecified.  Between the streams of two batches that use one snapshot
+ * through _dev variants, ordering is the caller's job. */
+int hsr_batch_snapshot_create(hsr_batch *b, int capacity, hsr_snapshot **out);
+void hsr_snapshot_destroy(hsr_snapshot *s);
+int hsr_snapshot_capacity(const hsr_snapshot *s);
+/* record slot[i] <- env env[i], i < n; a NULL env / slot array stands for 0..n-1 */
+int hsr_batch_snapshot_save(hsr_batch *b, hsr_snapshot *s, const int32_t *env, const int32_t *slot, int n);
+int hsr_batch_snapshot_save_dev(hsr_batch *b, hsr_snapshot *s, const int32_t *d_env, const int32_t *d_slot, int n);
+/* env env[i] <- record slot[i]; a slot may appear any number of times (fan-out) */
+int hsr_batch_snapshot_load(hsr_batch *b, const hsr_snapshot *s, const int32_t *slot, const int32_t *env, int n);
+int hsr_batch_snapshot_load_dev(hsr_batch *b, const hsr_snapshot *s, const int32_t *d_slot, const int32_t *d_env, int n);
+/* env dst[i] <- env src[i] inside one batch; every source is read before any destination is written (an env may be both), through a scratch
+ * snapshot of the batch that the first call allocates and a call with a larger n replaces (that call waits for the stream) */
+int hsr_batch_copy_envs(hsr_batch *b, const int32_t *src, const int32_t *dst, int n);
+int hsr_batch_copy_envs_dev(hsr_batch *b, const int32_t *d_src, const int32_t *d_dst, int n);
+/* Host image of a snapshot, for checkpoint files: a 56-byte little-endian header - "HSRSNAP1", u32 format version (1), u32 header bytes,
+ * u64 model fingerprint, i64 capacity, i32 nq nv nu nlink npair_sep (= max(npair, 1)), i32 record words - then uint32 [record words][capacity]
+ * as stored (record rows in the order above; csrc/snapshot.h).  export: len must be hsr_snapshot_image_bytes().  import / image_check return
+ * HSR_EBLOB, and import leaves the snapshot unchanged, for a wrong magic, version, fingerprint or size field, a capacity other than the
+ * snapshot's, and a len that is short, long or negative.  export and import wait for the whole device. */
+int hsr_snapshot_image_bytes(const hsr_snapshot *s, long long *out);
+int hsr_snapshot_export(const hsr_snapshot *s, void *out, long long len);
+int hsr_snapshot_import(hsr_snapshot *s, const void *image, long long len);
+/* no device work (usable without a GPU): 32-bit words per record; whether `image` is a snapshot image of model m (its capacity in *capacity, may be NULL) */
+int hsr_model_snapshot_record_words(const hsr_model *m);
+int hsr_model_snapshot_image_check(const hsr_model *m, const void *image, long long len, int *capacity);
 
 /* diagnostics (meaningful only in the -DHSR_PHASE_TIMING build, libhsrsim_timing.so; tools/phase_timing.py,
  * tools/block_times.py): per-phase cycle sums of the last launches, and per-workgroup
