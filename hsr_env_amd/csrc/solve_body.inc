@@ -672,8 +672,8 @@
             for (int j = 0; j < 6; j++) { cr[C2_GN + j] = o.gn[j]; cr[C2_U + j] = o.u[j]; }
             if (REP || !(CZG && c < KJ)) store_rows(rDw, adr, dim, o.dw);
         }
-        const float tot = gsum<G>(part);
-        const float unst = gsum<G>(unstable);
+        float tot, unst;
+        gsum2<G>(part, unstable, tot, unst);
         zones_changed = unst > 0.f; zones_flipped = unst >= 1024.f;
         wave_sync();
         return tot;
@@ -1032,7 +1032,9 @@
         float mv = 0;
         const BcSrc<G> bs_ = bc_prepare<G>(search_c);
         static_for<0, NK>([&](auto kc) { constexpr int k = decltype(kc)::value; fmac_bcast<G, k, bc_first<G, k, 0>()>(mv, Mrow[k], bs_); });
-        const float g1 = gsum<G>(search_c * (Ma_c - qfs_c)), g2 = gsum<G>(isdof ? search_c * mv : 0.f), snorm = fsqrt(gsum<G>(search_c * search_c));
+        float g1, g2, snorm2;
+        gsum3<G>(search_c * (Ma_c - qfs_c), isdof ? search_c * mv : 0.f, search_c * search_c, g1, g2, snorm2);
+        const float snorm = fsqrt(snorm2);
         PHASE(13);
         jmul(search_c, ls_jv);
         PHASE(25);
@@ -1084,8 +1086,10 @@
                     const float d1 = top ? 0.f : (bot ? Q1 + al * Q2 : d1m), d2 = top ? 0.f : (bot ? Q2 : d2m);
                     dp += d1; hp += d2;
                 }
-                dphi = g1 + al * g2 + gsum<G>(dp);
-                ddphi = g2 + gsum<G>(hp);
+                float sdp, shp;
+                gsum2<G>(dp, hp, sdp, shp);
+                dphi = g1 + al * g2 + sdp;
+                ddphi = g2 + shp;
             };
             const float gtol = tol * m.ls_tolerance * snorm / scale;
             float dp, hp, lo = 0, hi = -1;

@@ -188,6 +188,95 @@ template <int G> __device__ __forceinline__ int glast(int v) {   // value of the
     if constexpr (G == 16) return dpp_i<0x15F, false>(v); else return pick32_<31, 63>(v);
 }
 
+// Two / three group sums whose butterflies run side by side: a lone sum is a chain of four DPP adds that each wait two slots for
+// the one before (VALU write -> DPP read); with a second and a third sum in those slots they do work.  Every argument is pinned to
+// a register exactly as gsum pins its own, and every sum takes gsum's steps in gsum's order: each result is bit-identical to
+// gsum<G> of the same argument, in every lane.  For sums that are needed together; a sum that decides a branch before the
+// other is needed stays a gsum.
+#define HSR_GSUM_STAGE_(CTRL) do { const float ta_ = dpp_f<CTRL, true>(a), tb_ = dpp_f<CTRL, true>(b); a += ta_; b += tb_; } while (0)
+template <int G> __device__ __forceinline__ void gsum2(float a, float b, float &sa, float &sb) {
+    asm volatile("" : "+v"(a)); asm volatile("" : "+v"(b));
+    HSR_GSUM_STAGE_(0x128); HSR_GSUM_STAGE_(0x124); HSR_GSUM_STAGE_(0x122); HSR_GSUM_STAGE_(0x121);
+    if constexpr (G == 16) { sa = a; sb = b; }
+    else {
+        const unsigned ua = __builtin_bit_cast(unsigned, a), ub = __builtin_bit_cast(unsigned, b);
+        const auto wa = __builtin_amdgcn_permlane16_swap(ua, ua, false, false), wb = __builtin_amdgcn_permlane16_swap(ub, ub, false, false);
+        sa = __builtin_bit_cast(float, (unsigned)wa[0]) + __builtin_bit_cast(float, (unsigned)wa[1]);
+        sb = __builtin_bit_cast(float, (unsigned)wb[0]) + __builtin_bit_cast(float, (unsigned)wb[1]);
+    }
+}
+#undef HSR_GSUM_STAGE_
+#define HSR_GSUM_STAGE_(CTRL) do { const float ta_ = dpp_f<CTRL, true>(a), tb_ = dpp_f<CTRL, true>(b), tc_ = dpp_f<CTRL, true>(c); a += ta_; b += tb_; c += tc_; } while (0)
+template <int G> __device__ __forceinline__ void gsum3(float a, float b, float c, float &sa, float &sb, float &sc) {
+    asm volatile("" : "+v"(a)); asm volatile("" : "+v"(b)); asm volatile("" : "+v"(c));
+    HSR_GSUM_STAGE_(0x128); HSR_GSUM_STAGE_(0x124); HSR_GSUM_STAGE_(0x122); HSR_GSUM_STAGE_(0x121);
+    if constexpr (G == 16) { sa = a; sb = b; sc = c; }
+    else {
+        const unsigned ua = __builtin_bit_cast(unsigned, a), ub = __builtin_bit_cast(unsigned, b), uc = __builtin_bit_cast(unsigned, c);
+        const auto wa = __builtin_amdgcn_permlane16_swap(ua, ua, false, false), wb = __builtin_amdgcn_permlane16_swap(ub, ub, false, false);
+        const auto wc = __builtin_amdgcn_permlane16_swap(uc, uc, false, false);
+        sa = __builtin_bit_cast(float, (unsigned)wa[0]) + __builtin_bit_cast(float, (unsigned)wa[1]);
+        sb = __builtin_bit_cast(float, (unsigned)wb[0]) + __builtin_bit_cast(float, (unsigned)wb[1]);
+        sc = __builtin_bit_cast(float, (unsigned)wc[0]) + __builtin_bit_cast(float, (unsigned)wc[1]);
+    }
+}
+#undef HSR_GSUM_STAGE_
+
+// ONE PIVOT STEP of the 16-lane factorisations, as one asm statement.  Emitted piece by piece a step was a dependent chain with a pad
+// in front of every link (pivot broadcast, rsq, multiplies, first trailing update, forward term: nine wait states beside fifteen
+// instructions).  Here the step is software-pipelined and every distance the hardware asks for is filled with work of the step itself,
+// BY CONSTRUCTION - the compiler neither sees into the string nor can it move anything out of it:
+//   p holds the broadcast pivot on entry (formed by the step before) and the NEXT pivot on exit: row entry j + 1 is final after the
+//   first trailing update, so its broadcast is issued here and the rest of the run (the caller's fmac_bcast) follows it;
+//   the slot after v_rsq (a transcendental's result is not forwarded) carries the forward-substitution term of the step before;
+//   VALU write -> DPP read wants two independent slots: l = row[J] is read by the first update three slots after its multiply, and
+//   row[J + 1] by the pivot broadcast two slots (the two selects) after its update; t is read by the next step's forward term.
+// Same arithmetic, same operands, same order per value as the piecewise form (chol_g_fwd's 32-lane arm keeps that form).
+// FWD: t = sacc * inv (lane J: y_J) and, one step late, sacc -= L[c][J] y_J.  LAST: the column after which nothing is updated.
+#define HSR_DPPB_(n) " row_newbcast:%[" #n "] row_mask:0xf bank_mask:0xf\n\t"
+template <int J, bool LAST> __device__ __forceinline__ void chol_step16_fwd(float &p, float &rowj, float &rown, float &sacc, float &t, float &nl, float &invd, float &y, int c) {
+#define HSR_STEP_HEAD_ "v_mul_f32 %[l], %[l], %[p]\n\tv_mul_f32 %[t], %[sacc], %[p]\n\tv_xor_b32 %[nl], 0x80000000, %[l]\n\tv_cmp_eq_u32 vcc, %[j], %[c]\n\t"
+#define HSR_STEP_SEL_ "v_cndmask_b32 %[invd], %[invd], %[p], vcc\n\tv_cndmask_b32 %[y], %[y], %[t], vcc\n\t"
+    if constexpr (J == 0) {
+        static_assert(!LAST, "a one-column matrix needs no step");
+        asm volatile("v_rsq_f32 %[p], %[p]\n\ts_nop 0\n\t" HSR_STEP_HEAD_ "v_fmac_f32_dpp %[n], %[l], %[nl]" HSR_DPPB_(jn) HSR_STEP_SEL_ "v_mov_b32_dpp %[p], %[n]" HSR_DPPB_(jn)
+                     : [p] "+v"(p), [l] "+v"(rowj), [n] "+v"(rown), [t] "=&v"(t), [nl] "=&v"(nl), [invd] "+v"(invd), [y] "+v"(y)
+                     : [sacc] "v"(sacc), [c] "v"(c), [j] "n"(J), [jn] "n"(J + 1) : "vcc");
+    } else if constexpr (!LAST) {
+        asm volatile("v_rsq_f32 %[p], %[p]\n\tv_fmac_f32_dpp %[sacc], %[t], %[nl]" HSR_DPPB_(jp) HSR_STEP_HEAD_ "v_fmac_f32_dpp %[n], %[l], %[nl]" HSR_DPPB_(jn) HSR_STEP_SEL_ "v_mov_b32_dpp %[p], %[n]" HSR_DPPB_(jn)
+                     : [p] "+v"(p), [l] "+v"(rowj), [n] "+v"(rown), [sacc] "+v"(sacc), [t] "+v"(t), [nl] "+v"(nl), [invd] "+v"(invd), [y] "+v"(y)
+                     : [c] "v"(c), [j] "n"(J), [jn] "n"(J + 1), [jp] "n"(J - 1) : "vcc");
+    } else {
+        asm volatile("v_rsq_f32 %[p], %[p]\n\tv_fmac_f32_dpp %[sacc], %[t], %[nl]" HSR_DPPB_(jp) HSR_STEP_HEAD_ HSR_STEP_SEL_
+                     : [p] "+v"(p), [l] "+v"(rowj), [sacc] "+v"(sacc), [t] "+v"(t), [nl] "+v"(nl), [invd] "+v"(invd), [y] "+v"(y)
+                     : [c] "v"(c), [j] "n"(J), [jp] "n"(J - 1) : "vcc");
+    }
+#undef HSR_STEP_HEAD_
+#undef HSR_STEP_SEL_
+}
+// ... without a right-hand side (chol_g_tail).  T = number of trailing updates of the step; the first three are part of the statement
+// (they are what separates the update of row[J + 1] from its broadcast; with fewer, pads make up the two slots).
+template <int J, int T> __device__ __forceinline__ void chol_step16(float &p, float &rowj, float &r1, float &r2, float &r3, float &nl, float &invd, int c) {
+#define HSR_STEP_HEAD_ "v_rsq_f32 %[p], %[p]\n\tv_cmp_eq_u32 vcc, %[j], %[c]\n\tv_mul_f32 %[l], %[l], %[p]\n\tv_xor_b32 %[nl], 0x80000000, %[l]\n\tv_cndmask_b32 %[invd], %[invd], %[p], vcc\n\t"
+    if constexpr (T >= 3) {
+        asm volatile(HSR_STEP_HEAD_ "v_fmac_f32_dpp %[n1], %[l], %[nl]" HSR_DPPB_(j1) "v_fmac_f32_dpp %[n2], %[l], %[nl]" HSR_DPPB_(j2) "v_fmac_f32_dpp %[n3], %[l], %[nl]" HSR_DPPB_(j3) "v_mov_b32_dpp %[p], %[n1]" HSR_DPPB_(j1)
+                     : [p] "+v"(p), [l] "+v"(rowj), [n1] "+v"(r1), [n2] "+v"(r2), [n3] "+v"(r3), [nl] "=&v"(nl), [invd] "+v"(invd)
+                     : [c] "v"(c), [j] "n"(J), [j1] "n"(J + 1), [j2] "n"(J + 2), [j3] "n"(J + 3) : "vcc");
+    } else if constexpr (T == 2) {
+        asm volatile(HSR_STEP_HEAD_ "v_fmac_f32_dpp %[n1], %[l], %[nl]" HSR_DPPB_(j1) "v_fmac_f32_dpp %[n2], %[l], %[nl]" HSR_DPPB_(j2) "s_nop 0\n\tv_mov_b32_dpp %[p], %[n1]" HSR_DPPB_(j1)
+                     : [p] "+v"(p), [l] "+v"(rowj), [n1] "+v"(r1), [n2] "+v"(r2), [nl] "=&v"(nl), [invd] "+v"(invd)
+                     : [c] "v"(c), [j] "n"(J), [j1] "n"(J + 1), [j2] "n"(J + 2) : "vcc");
+    } else if constexpr (T == 1) {
+        asm volatile(HSR_STEP_HEAD_ "v_fmac_f32_dpp %[n1], %[l], %[nl]" HSR_DPPB_(j1) "s_nop 1\n\tv_mov_b32_dpp %[p], %[n1]" HSR_DPPB_(j1)
+                     : [p] "+v"(p), [l] "+v"(rowj), [n1] "+v"(r1), [nl] "=&v"(nl), [invd] "+v"(invd)
+                     : [c] "v"(c), [j] "n"(J), [j1] "n"(J + 1) : "vcc");
+    } else {
+        asm volatile(HSR_STEP_HEAD_ : [p] "+v"(p), [l] "+v"(rowj), [nl] "=&v"(nl), [invd] "+v"(invd) : [c] "v"(c), [j] "n"(J) : "vcc");
+    }
+#undef HSR_STEP_HEAD_
+}
+#undef HSR_DPPB_
+
 // in-register cooperative Cholesky: lane c holds row c (entries k <= c) of an SPD matrix; on return row c of L in
 // row[0..c] (entries k > c are scratch) and invd = 1 / L[c][c].  Columns j >= ndense are known to have no
 // off-diagonal entries (block-diagonal tail of M): only their pivots are taken.
@@ -231,6 +320,19 @@ template <int G, int NK = G> __device__ __forceinline__ bool chol_g_fwd(float (&
     // the lane id is laundered per call: the thirteen `c == j` masks are then formed where they are used (one v_cmp each) instead of being hoisted out of
     // the Newton loop as SGPR pairs, spilled into VGPR lanes and read back with two v_readlane per step
     asm volatile("" : "+v"(c));
+    if constexpr (G == 16 && NK > 1) {
+        // one asm statement per pivot step (chol_step16_fwd): the step forms the next pivot's broadcast and the forward term of the step before
+        float p = gbcast_after_asm<G, 0>(row[0]), t = 0.f, nl = 0.f;
+        static_for<0, NK>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if (j < nv) {
+                chol_step16_fwd<j, j == NK - 1>(p, row[j], row[j + 1 < NK ? j + 1 : j], sacc, t, nl, invd, y, c);
+                const BcSrc<G> bl = bc_prepare<G>(row[j]);
+                static_for<j + 2, NK>([&](auto ic) { constexpr int i = decltype(ic)::value; fmac_bcast<G, i>(row[i], nl, bl); });      // (row[j], nl: written four and more slots ago)
+            }
+        });       // (the last step's forward term would only feed lanes that have taken their y: not formed)
+        return chol_pivots_ok<G>(invd);
+    } else
     static_for<0, NK>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         if (j < nv) {
@@ -417,6 +519,15 @@ struct HessAcc32 {
 template <int G, int NK, int ND> __device__ __forceinline__ bool chol_g_tail(float (&row)[G], float &invd, float diag, int c) {
     asm volatile("" : "+v"(c));          // lane masks formed where they are used, not hoisted out of the caller's loops as spilled SGPR pairs (chol_g_fwd)
     invd = 1.f;
+    if constexpr (G == 16 && ND > 0) {
+        float p = gbcast_after_asm<G, 0>(row[0]), nl;
+        static_for<0, ND>([&](auto jc) {
+            constexpr int j = decltype(jc)::value, T = ND - 1 - j;
+            chol_step16<j, T>(p, row[j], row[T >= 1 ? j + 1 : j], row[T >= 2 ? j + 2 : j], row[T >= 3 ? j + 3 : j], nl, invd, c);
+            const BcSrc<G> bl = bc_prepare<G>(row[j]);
+            static_for<j + 4, ND>([&](auto ic) { constexpr int i = decltype(ic)::value; fmac_bcast<G, i>(row[i], nl, bl); });
+        });
+    } else
     static_for<0, ND>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         const float ajj = gbcast_after_asm<G, j>(row[j]);

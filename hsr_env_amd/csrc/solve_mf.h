@@ -55,7 +55,8 @@ template <int G, int NK = G> __device__ __forceinline__ float chol_solve_mf(cons
     static_for<0, NK / 2>([&](auto jc) {
         constexpr int j = NK - 1 - 2 * decltype(jc)::value;           // columns j and j - 1
         if (j - 1 < nv) {
-            const float A = gsum<G>(nlo[j] * x), B = gsum<G>(nlo[j - 1] * x);
+            float A, B;
+            gsum2<G>(nlo[j] * x, nlo[j - 1] * x, A, B);
             const float xj = (j < nv) ? (y + A) * invd : 0.f;
             if (c == j) x = xj;
             const float t = gbcast<G, j>(nlo[j - 1] * xj);
@@ -78,7 +79,8 @@ template <int G, int NK = G> __device__ __forceinline__ float chol_back_mf(const
     static_for<0, NK / 2>([&](auto jc) {
         constexpr int j = NK - 1 - 2 * decltype(jc)::value;
         if (j - 1 < nv) {
-            const float A = gsum<G>(nlo[j] * x), B = gsum<G>(nlo[j - 1] * x);
+            float A, B;
+            gsum2<G>(nlo[j] * x, nlo[j - 1] * x, A, B);
             const float xj = (j < nv) ? (y + A) * invd : 0.f;
             if (c == j) x = xj;
             const float t = gbcast<G, j>(nlo[j - 1] * xj);
