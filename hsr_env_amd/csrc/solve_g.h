@@ -543,7 +543,7 @@ template <int G, int NK, int ND> __device__ __forceinline__ bool chol_g_tail(flo
     return chol_pivots_ok<G>(invd);
 }
 // elliptic cone at residual x: cost, gradient g, and the Hessian in the form
-//   H = diag(dw) + Dm gn gn^T - k3 u u^T      (zone 0 top: all zero; 1 bottom: dw = D; 2 middle)
+//   H = diag(dw) + Dm gn gn^T - k3 u u^T      (zone 0 top: all zero; 1 bottom: dw = D; 2 middle; k3 and u only mean something as this product)
 // The three cone functions take their six rows ZERO-PADDED: D[j] = x[j] = v[j] = 0 and fri[j - 1] = 0 for the rows j >= dim a contact
 // does not have (cone_rows / cone_fri in solve_body.inc) - every formula then yields 0 for them by itself, and no per-row test on dim
 // (six exec-mask branches per call) is needed.
@@ -568,12 +568,16 @@ __device__ __forceinline__ void cone_eval2(int /*dim*/, float mu, const float *f
     o.zone = 2;
     const float Dm = D[0] * frcp(mu * mu * (1 + mu * mu)), NT = Nn - mu * T, invT = frcp(T);
     const float kappa = -Dm * NT * mu;
-    o.Dm = Dm; o.k3 = kappa * invT * frcp(T2);
+    // k3 = kappa / T^3 leaves the float range long before T^2 does (Dm mu^2 / T^2: T < 1e-16 with D = 1e6) while k3 u u^T stays of the order of Dm mu^2:
+    // below T^2 = 2^-64 the pair is kept as (k3 2^-80, u 2^40) - the same product, powers of two, so nothing is rounded; above, the factors are 1
+    const bool tiny = T2 < 0x1p-64f;
+    const float us = tiny ? 0x1p40f : 1.f, ts = tiny ? 0x1p80f : 1.f;
+    o.Dm = Dm; o.k3 = kappa * invT * frcp(T2 * ts);
     o.gn[0] = mu;
 #pragma unroll
     for (int j = 1; j < 6; j++) {
         o.gn[j] = -mu * U[j] * fri[j - 1] * invT;
-        o.u[j] = fri[j - 1] * U[j];
+        o.u[j] = fri[j - 1] * U[j] * us;
         o.dw[j] = kappa * fri[j - 1] * fri[j - 1] * invT;
     }
 #pragma unroll
@@ -619,7 +623,9 @@ __device__ __forceinline__ void cone_dd(int /*dim*/, float mu, const float *fri,
     const float Dm = D[0] * frcp(mu * mu * (1 + mu * mu)), NT = Nn - mu * T, invT = frcp(T);
     const float kappa = -Dm * NT * mu, gnv = mu * (v[0] - invT * S1);
     d1 = Dm * NT * gnv;
-    d2 = kappa * invT * S2 + Dm * gnv * gnv - (kappa * invT * frcp(T2)) * S1 * S1;
+    const bool tiny = T2 < 0x1p-64f;          // (cone_eval2: k3 alone overflows where k3 S1^2 does not)
+    const float S1s = S1 * (tiny ? 0x1p40f : 1.f), ts = tiny ? 0x1p80f : 1.f;
+    d2 = kappa * invT * S2 + Dm * gnv * gnv - (kappa * invT * frcp(T2 * ts)) * S1s * S1s;
 }
 
 enum { NLMAX = 16 };

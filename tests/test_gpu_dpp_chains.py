@@ -2,7 +2,9 @@
 the back substitutions) against frozen copies of the routines as they were: tools/micro/dpp_chains.hip factors and solves 256 seeded SPD matrices
 (column scales over 1e-3 .. 1e3, one with a non-positive pivot in the middle) with both and compares row[0..c], invd, y and x word by word - the
 cfg3 instance (G = 16, NK = 13), the block-diagonal tail (ND = 7) and the 32-lane instance (NK = 25) whose broadcast runs cross lane 16 - and every
-multi-sum against gsum in every lane, also with every second lane group switched off.  Only the order of issue may differ: not one bit of a result."""
+multi-sum against gsum in every lane, also with every second lane group switched off.  Only the order of issue may differ: not one bit of a result.
+This module pins the BITS: a mistake that the rewritten and the frozen routine share passes here.  What the routines compute - that the factor is a
+Cholesky factor and the solves solve, within Higham's bounds, for every instantiation and run-time nv / ndense - is pinned by tests/test_gpu_lane_groups.py."""
 import shutil
 import subprocess
 from pathlib import Path
