@@ -28,6 +28,7 @@
 #include "render.h"
 #include "episode.h"
 #include "snapshot.h"
+#include "replay.h"
 #include "cfg_consts.h"
 
 #include "host_model.h"      // error message, blob loader, hsr_model_*, hull planes: plain C++, no HIP
@@ -39,3 +40,4 @@
 #include "host_access.h"     // settings, state / field getters and setters, diagnostics
 #include "host_render.h"     // ray-caster front end and in-step frame capture
 #include "host_snapshot.h"   // env records on the device: save / load / env-to-env copy, the host image (kernel: snapshot.h)
+#include "host_replay.h"     // hindsight replay: the transition ring and its sampler (kernels: replay.h; books and checks: replay_logic.h)

@@ -94,6 +94,7 @@ class VecHSREnv:
         if self.auto_reset and not hasattr(sim, "set_episodes"):
             raise NotImplementedError("auto_reset=True needs a simulator handle with set_episodes (BatchSim): episodes run on the device")
         self._dev = None
+        self._replay = None            # make_replay(): the hindsight replay the device loop feeds
         # hsr/env.py:50-66: record when any of record / record_path / record_freq is given.  One video per recorded env (global ids
         # record_envs, default [0]; a rank records the ones in its shard) under the directory record_path (record.py)
         self._recorder = None
@@ -257,7 +258,10 @@ class VecHSREnv:
         self._begin_goals()
         self.sim.reset_sampled(m)
         self._refresh_goal_points()
-        return self._get_observation()
+        obs = self._get_observation()
+        if self._replay is not None:
+            self._replay_commit_host(self._last_obs, m)
+        return obs
 
     def _device_buffers(self):
         """torch tensors on the batch's device and the batch's stream as a torch stream: what the device loop reads and writes."""
@@ -270,6 +274,8 @@ class VecHSREnv:
                              final=f32(n, no), rew=f32(n), fret=f32(n), done=torch.zeros(n, dtype=torch.uint8, device=dev),
                              kind=torch.zeros(n, dtype=torch.uint8, device=dev), ns=torch.zeros(n, dtype=torch.int32, device=dev),
                              flen=torch.zeros(n, dtype=torch.int32, device=dev))
+            if self._replay is not None:                                # rows handed to the replay that no other buffer holds
+                self._dev.update(robs=f32(n, self.obs_dim), rmask=torch.zeros(n, dtype=torch.uint8, device=dev))
             torch.cuda.synchronize(dev)                                 # the fills ran on torch's stream, the batch has its own
         return self._dev
 
@@ -302,7 +308,15 @@ class VecHSREnv:
             if self._recorder is not None:
                 self._recorder.after_step(d["done"].cpu().numpy().astype(bool), d["ns"].cpu().numpy())
             final = self.sim.obs_openai() if self._obs_type == "openai" else None       # before the reset moves the bodies
+            if self._replay is not None:                                                # likewise: the achieved goal is read from the poses of this step
+                if final is not None:
+                    self.sim.obs_openai_dev(d["robs"].data_ptr())
+                self._replay.record(d["ctrl"], d["obs"] if final is None else d["robs"], d["rew"], d["done"])
             self.sim.episode_end_dev(ptr["obs"], ptr["rew"], ptr["done"], ptr["final"] if final is None else None, ptr["kind"], ptr["fret"], ptr["flen"])
+            if self._replay is not None:
+                if final is not None:
+                    self.sim.obs_openai_dev(d["robs"].data_ptr())                       # the first observation of the envs that were reset
+                self._replay.commit(d["obs"] if final is None else d["robs"], d["kind"])
             host = {k: d[k].cpu().numpy() for k in ("obs", "rew", "done", "ns", "kind", "fret", "flen")}
             if final is None:
                 final = d["final"].cpu().numpy()
@@ -329,6 +343,46 @@ class VecHSREnv:
             return obs[0], float(host["rew"][0]), bool(reset[0]), info
         return obs, host["rew"], reset, info
 
+    # ------------------------------------------------------------------ hindsight replay on the device (replay.py)
+    def make_replay(self, capacity_steps: int, her_ratio: float = 0.8, seed: Optional[int] = None):
+        """Attach a replay.HindsightReplay to the device loop and return it: from now on every step() records its transition (between the
+        step and the episode end, so the achieved goal is the one of the step, not of the next episode's start) and commits the
+        observation it returns, and reset() commits too; ``replay.sample(batch_size)`` then draws relabelled minibatches without a copy
+        to the host.  Rows are this env's observations (25 floats with obs_type='openai').  seed None: the env's seed."""
+        if not self.auto_reset:
+            raise ValueError("make_replay needs auto_reset=True: the replay is fed by the device loop, which only that mode runs")
+        if self._point_goal is None:
+            raise NotImplementedError("make_replay needs a point goal (a body and a point): hindsight relabelling replaces that point by a "
+                                      "position the body reached")
+        if self._extra_terms:
+            raise NotImplementedError("make_replay with body-body goals besides the point goal: their reward cannot be recomputed from a relabelled point")
+        if self._replay is not None:
+            raise ValueError("this env already feeds a replay")
+        from .replay import HindsightReplay
+        self._replay = HindsightReplay(self.sim, capacity_steps, self._goal_body, self._geofence, obs_dim=self.obs_dim, her_ratio=her_ratio,
+                                       seed=self._seed if seed is None else seed, env_offset=self.env_offset)
+        self._dev = None                                                # the buffers gain the replay's staging rows
+        self._get_observation()
+        self._replay_commit_host(self._last_obs, None)
+        return self._replay
+
+    def _replay_commit_host(self, obs, mask):
+        """commit() of host rows: the observation reset() returns, and the envs it began an episode for."""
+        import torch
+        d = self._device_buffers()
+        with torch.cuda.stream(d["stream"]):
+            d["robs"].copy_(torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32).reshape(self.n_envs, self.obs_dim)))
+            if mask is not None:
+                d["rmask"].copy_(torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.n_envs)))
+            self._replay.commit(d["robs"], None if mask is None else d["rmask"])
+            d["stream"].synchronize()                                   # the host rows are pageable: the copies must not outlive them
+
+    def _replay_restart(self):
+        """After a jump (load_state, fork) the ring describes a past the envs no longer have: forget it and start from the current rows."""
+        if self._replay is not None:
+            self._replay.clear()
+            self._replay_commit_host(self._last_obs, None)
+
     # ------------------------------------------------------------------ exact snapshots (sim.Snapshot; DESIGN.md)
     def _no_jump_while_recording(self, what):
         if self._recorder is not None:
@@ -344,7 +398,8 @@ class VecHSREnv:
                         self._last_obs.copy(), self.goals is not None)
 
     def load_state(self, state: EnvState):
-        """sim.set_state() in its exact form (hsr/env.py:175; hsr/mujoco_env.py:87-94): no forward pass, nothing recomputed."""
+        """sim.set_state() in its exact form (hsr/env.py:175; hsr/mujoco_env.py:87-94): no forward pass, nothing recomputed.  A replay made by
+        make_replay() is cleared: a ring of past transitions cannot follow a jump."""
         self._no_jump_while_recording("load_state")
         if state.began != (self.goals is not None):
             raise ValueError("load_state: the state was saved on the other side of the first reset()")
@@ -356,10 +411,12 @@ class VecHSREnv:
             self._action_step = state.action_step
         self._last_obs = state.last_obs.copy()
         self._publish_goal_points()
+        self._replay_restart()
 
     def fork(self, src, dst):
         """Envs `dst` become copies of env(s) `src` (one id for all, or one per destination), on the device, and continue bit for bit as
-        their sources do; with auto_reset=True their next episodes are drawn with their own env ids."""
+        their sources do; with auto_reset=True their next episodes are drawn with their own env ids.  A replay made by make_replay() is
+        cleared: a ring of past transitions cannot follow a jump."""
         self._no_jump_while_recording("fork")
         dst = np.atleast_1d(np.asarray(dst, dtype=np.int32))
         src = np.broadcast_to(np.asarray(src, dtype=np.int32), dst.shape).copy()
@@ -368,6 +425,7 @@ class VecHSREnv:
         self._goal_points[dst] = self._goal_points[src]
         self._last_obs[dst] = self._last_obs[src]
         self._publish_goal_points()
+        self._replay_restart()
 
     def set_state(self, qpos, qvel):
         qpos = np.asarray(qpos, dtype=np.float32).reshape(self.n_envs, -1)

@@ -1,0 +1,97 @@
+"""Hindsight experience replay on the device (include/hsrsim.h: hsr_replay; DESIGN.md "Hindsight replay on the device").
+
+The reference's task is sparse-reward and goal-conditioned - ``reward = float(block within geofence of a sampled point)``
+(hsr/env.py:124-133), a new point every episode (hsr/env.py:161-172), observations meant as ``Obs(observation, goal)`` (hsr/env.py:275) -
+and its host ring (rl_utils/replay_buffer.py:27-82) knows nothing of episodes.  ``HindsightReplay`` keeps the transitions of every env of a
+``BatchSim`` on the device, episode by episode, and draws minibatches whose goals are relabelled with the 'future' strategy (Andrychowicz
+et al., "Hindsight Experience Replay", NIPS 2017) and whose reward and done are recomputed by the env's own goal test.  Nothing visits
+the host; a minibatch is a pure function of (seed, draw counter, ring contents).
+
+Plumbing only: the kernels are csrc/replay.h.  There is no CPU stand-in.
+"""
+from __future__ import annotations
+
+from .sim import BatchSim, ReplaySpec
+
+
+class HindsightReplay:
+    """Ring of the last `capacity_steps` transitions of every env of `sim`.
+
+    Per env-step: ``record(ctrl, next_obs, reward, done)`` after ``sim.step_dev`` and before ``sim.episode_end_dev`` / any reset (the goal
+    body's position is read from the batch at that moment), then ``commit(obs, reset)`` with the observation the policy acts on next and
+    the envs that start a new episode with it.  ``sample(batch_size)`` may run whenever no record waits for its commit.
+    Arguments are torch tensors on the batch's device (float32, uint8 for done / reset; reward / done None: what the step latched)."""
+
+    def __init__(self, sim: BatchSim, capacity_steps: int, goal_body: int, geofence: float, obs_dim: int = None, her_ratio: float = 0.8,
+                 seed: int = 0, env_offset: int = 0):
+        import torch
+        if not 0.0 <= float(her_ratio) <= 1.0:
+            raise ValueError("her_ratio must lie in [0, 1]")
+        self.sim, self.her_ratio = sim, float(her_ratio)
+        self.capacity_steps, self.obs_dim = int(capacity_steps), int(sim.nq + sim.nv if obs_dim is None else obs_dim)
+        spec = ReplaySpec(seed=int(seed) & (2 ** 64 - 1), env_offset=int(env_offset) & 0xffffffff, capacity_steps=self.capacity_steps,
+                          obs_dim=self.obs_dim, goal_body=int(goal_body), geofence=float(geofence))
+        self._replay = sim.replay(spec)
+        self._device = torch.device("cuda", getattr(sim, "device", 0))
+        self._stream = torch.cuda.ExternalStream(sim.stream_ptr(), device=self._device)
+        self._buffers = {}             # batch size -> the output tensors, allocated once
+        self._draw = 0
+
+    def _ptr(self, t, shape, dtype):
+        if t is None:
+            return None
+        if tuple(t.shape) != shape or str(t.dtype) != dtype or not t.is_contiguous() or t.device != self._device:
+            raise AssertionError(f"replay: expected a contiguous {dtype} tensor of shape {shape} on {self._device}")
+        return t.data_ptr()
+
+    def commit(self, obs, reset=None):
+        n = self.sim.n
+        self._replay.commit_dev(self._ptr(obs, (n, self.obs_dim), "torch.float32"), self._ptr(reset, (n,), "torch.uint8"))
+
+    def record(self, ctrl, next_obs, reward=None, done=None):
+        n = self.sim.n
+        self._replay.record_dev(self._ptr(ctrl, (n, self.sim.nu), "torch.float32"), self._ptr(next_obs, (n, self.obs_dim), "torch.float32"),
+                                self._ptr(reward, (n,), "torch.float32"), self._ptr(done, (n,), "torch.uint8"))
+
+    def sample(self, batch_size: int) -> dict:
+        """The next minibatch: obs [B, obs_dim], action [B, nu], next_obs, goal [B, 3], achieved_next [B, 3], reward [B] (float32), done [B]
+        (uint8) and index [B, 4] (int32: env, slot, goal slot or -1, relabelled), written on the batch's stream into tensors that the next
+        sample() of the same size overwrites.  Order torch work after it with ``torch.cuda.stream(replay.stream)`` or a stream wait."""
+        import torch
+        b = int(batch_size)
+        out = self._buffers.get(b)
+        if out is None:
+            f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self._device)
+            out = dict(obs=f32(b, self.obs_dim), action=f32(b, self.sim.nu), next_obs=f32(b, self.obs_dim), goal=f32(b, 3), achieved_next=f32(b, 3),
+                       reward=f32(b), done=torch.zeros(b, dtype=torch.uint8, device=self._device),
+                       index=torch.zeros((b, 4), dtype=torch.int32, device=self._device))
+            torch.cuda.synchronize(self._device)       # the fills ran on torch's stream, the batch has its own
+            self._buffers[b] = out
+        p = {k: v.data_ptr() for k, v in out.items()}
+        self._replay.sample_dev(self._draw, b, self.her_ratio, p["obs"], p["action"], p["next_obs"], p["goal"], p["achieved_next"], p["reward"],
+                                p["done"], p["index"])
+        self._draw = (self._draw + 1) & 0xffffffff
+        return out
+
+    @property
+    def stream(self):
+        """The batch's stream as a torch stream: where record / commit / sample run."""
+        return self._stream
+
+    def state(self):
+        """(count, head slot, pushed & 0xffffffff) from the host books."""
+        return self._replay.state()
+
+    def clear(self):
+        """Forget every transition and episode (the storage stays); the next call must be commit()."""
+        self._replay.clear()
+
+    def close(self):
+        self._replay.close()
+        self._buffers = {}
+
+    def __len__(self):
+        return self._replay.state()[0] * self.sim.n
+
+
+__all__ = ["HindsightReplay", "ReplaySpec"]

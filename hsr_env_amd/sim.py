@@ -110,6 +110,13 @@ PROTOTYPES = {
     "hsr_snapshot_import": (_int, [_vp, C.c_char_p, C.c_longlong]),
     "hsr_model_snapshot_record_words": (_int, [_vp]),
     "hsr_model_snapshot_image_check": (_int, [_vp, C.c_char_p, C.c_longlong, _ip]),
+    "hsr_batch_replay_create": (_int, [_vp, _vp, C.POINTER(_vp)]),
+    "hsr_replay_destroy": (None, [_vp]),
+    "hsr_replay_clear": (_int, [_vp]),
+    "hsr_replay_commit_dev": (_int, [_vp, _vp, _vp]),
+    "hsr_replay_record_dev": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "hsr_replay_state": (_int, [_vp, _i32p, _i32p, C.POINTER(C.c_uint32)]),
+    "hsr_replay_sample_dev": (_int, [_vp, C.c_uint32, _int, _float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = list(PROTOTYPES)
 
@@ -240,6 +247,11 @@ class BatchSim:
     def snapshot(self, capacity=None) -> "Snapshot":
         """Device storage for `capacity` env records (default: one per env), bound to this batch's model and device."""
         return Snapshot(self, self.n if capacity is None else capacity)
+
+    # -- hindsight replay (include/hsrsim.h: hsr_batch_replay_create ..; the class Replay below, replay.HindsightReplay on top of it)
+    def replay(self, spec: "ReplaySpec") -> "Replay":
+        """An episode-aware transition ring on the device with a relabelling sampler, bound to this batch."""
+        return Replay(self, spec)
 
     def copy_envs(self, src, dst):
         """env dst[i] <- env src[i] on the device, every source read before any destination is written; the destinations then continue
@@ -607,3 +619,48 @@ class Snapshot:
         cap = C.c_int(0)
         _check(L, L.hsr_model_snapshot_image_check(sim._m, bytes(data), len(data), C.byref(cap)))
         return cls(sim, cap.value)._from_image(data)
+
+
+class ReplaySpec(C.Structure):
+    """include/hsrsim.h: hsr_replay_spec."""
+    _fields_ = [("seed", C.c_uint64), ("env_offset", C.c_uint32), ("capacity_steps", C.c_int32), ("obs_dim", C.c_int32),
+                ("goal_body", C.c_int32), ("geofence", C.c_float)]
+
+
+class Replay:
+    """The transition ring of a batch (include/hsrsim.h: hsr_replay) as the library exposes it: device pointers in, asynchronous on the
+    batch stream.  Its storage is released by close() or by close() of its batch, whichever comes first."""
+
+    def __init__(self, sim: BatchSim, spec: ReplaySpec):
+        self.sim, self.spec = sim, spec
+        self._r = C.c_void_p()
+        _check(sim._L, sim._L.hsr_batch_replay_create(sim._b, C.byref(spec), C.byref(self._r)))
+
+    def close(self):
+        if getattr(self, "_r", None):
+            self.sim._L.hsr_replay_destroy(self._r); self._r = None
+
+    __del__ = close
+
+    def clear(self):
+        _check(self.sim._L, self.sim._L.hsr_replay_clear(self._r))
+
+    def commit_dev(self, d_obs, d_reset=None):
+        """d_obs float32 [N, obs_dim]: what the policy acts on next; d_reset uint8 [N]: the envs that start an episode with it (None: all)."""
+        _check(self.sim._L, self.sim._L.hsr_replay_commit_dev(self._r, d_obs, d_reset))
+
+    def record_dev(self, d_ctrl, d_next_obs, d_reward=None, d_done=None):
+        """After step_dev and before episode_end_dev: the transition of every env into the ring's head slot."""
+        _check(self.sim._L, self.sim._L.hsr_replay_record_dev(self._r, d_ctrl, d_next_obs, d_reward, d_done))
+
+    def state(self):
+        """(count, head slot, pushed & 0xffffffff): the host books, no device work."""
+        c, h, p = C.c_int32(0), C.c_int32(0), C.c_uint32(0)
+        _check(self.sim._L, self.sim._L.hsr_replay_state(self._r, C.byref(c), C.byref(h), C.byref(p)))
+        return int(c.value), int(h.value), int(p.value)
+
+    def sample_dev(self, draw, batch, her_ratio, d_obs=None, d_act=None, d_next_obs=None, d_goal=None, d_achieved_next=None, d_reward=None,
+                   d_done=None, d_index=None):
+        """Minibatch `draw` of `batch` samples into device arrays (any None); include/hsrsim.h states the function."""
+        _check(self.sim._L, self.sim._L.hsr_replay_sample_dev(self._r, int(draw) & 0xffffffff, int(batch), float(her_ratio), d_obs, d_act, d_next_obs,
+                                                              d_goal, d_achieved_next, d_reward, d_done, d_index))

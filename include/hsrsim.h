@@ -30,6 +30,7 @@ extern "C" {
 typedef struct hsr_model hsr_model;
 typedef struct hsr_batch hsr_batch;
 typedef struct hsr_snapshot hsr_snapshot;
+typedef struct hsr_replay hsr_replay;
 
 /* indices for hsr_model_size() */
 enum hsr_size { HSR_NQ = 0, HSR_NV, HSR_NU, HSR_NLINK, HSR_NBODY, HSR_NGEOM, HSR_NPAIR, HSR_NMESHVERT,
@@ -282,7 +283,8 @@ int hsr_batch_episode_state(hsr_batch *b, uint32_t *ep_index, int32_t *ep_length
  *   an env's next episode is drawn with key (gid of the env it was loaded into, restored episode index).
  * A loaded env continues bit for bit as the saved one did, in any slot of any batch of the same model (results never depend on either).
  * NOT in a record: the solver's and the narrowphase's intermediates (for a loaded env hsr_batch_get_field other than HSR_F_XPOS / HSR_F_XMAT
- * describes nothing until the next forward or step), capture slots and frames, goals, settings, cap statistics.
+ * describes nothing until the next forward or step), capture slots and frames, goals, settings, cap statistics, and a hindsight replay
+ * (below: a ring of past transitions cannot follow a jump; clear it after a load or a copy).
  * Records are copied as 32-bit patterns (NaN payloads and -0 survive).  A snapshot is bound to a model (the 64-bit FNV-1a hash of its blob,
  * computed by hsr_model_load) and a device, not to the batch that made it: it may be loaded into another batch of the same model on the
  * same device.  Its device storage is released by hsr_snapshot_destroy, or by hsr_batch_destroy of the batch that made it, whichever
@@ -318,6 +320,65 @@ int hsr_snapshot_import(hsr_snapshot *s, const void *image, long long len);
 /* no device work (usable without a GPU): 32-bit words per record; whether `image` is a snapshot image of model m (its capacity in *capacity, may be NULL) */
 int hsr_model_snapshot_record_words(const hsr_model *m);
 int hsr_model_snapshot_image_check(const hsr_model *m, const void *image, long long len, int *capacity);
+
+/* ---- hindsight replay on the device: an episode-aware transition ring and a relabelling sampler ----------------------------------------
+ * Opt-in.  The task is sparse-reward and goal-conditioned: reward = float(goal body within the geofence of the sampled point)
+ * (hsr/env.py:124-133,137-147), a new point every episode (hsr/env.py:161-172), observations meant as the pair (observation, goal)
+ * (hsr/env.py:275).  A replay replaces the host ring of rl_utils/replay_buffer.py:27-82 (store, sample) for this env and adds what hindsight
+ * relabelling needs and only the batch has: the goal body's position after the step and before the auto-reset moves it, mocap_pos, and
+ * where an episode ends inside the ring.
+ *
+ * Ownership as for snapshots: a replay is bound to the batch that made it, reads that batch's arrays and launches on hsr_batch_stream().
+ * Its storage goes with hsr_replay_destroy, or with hsr_batch_destroy of its batch, whichever is first: after the latter the handle is
+ * still the caller's to destroy, and every other use returns HSR_EINVAL.  A batch that never creates one allocates nothing.  A replay is
+ * NOT part of an env record (snapshots above): after hsr_batch_snapshot_load* / hsr_batch_copy_envs* the ring describes a past the envs no
+ * longer have - clear it.
+ *
+ * Storage per env: capacity_steps rows of W = 2 obs_dim + nu + 10 words (padded to a multiple of 4):
+ *   obs | act | next_obs | achieved_next[3] | desired[3] | reward | done | ep_id | ep_step
+ * Protocol (host state machine EMPTY -> READY -> PENDING; a call out of order returns HSR_EINVAL and launches nothing):
+ *   commit(d_obs [N,obs_dim], d_reset [N] or NULL = all): d_obs is what the policy acts on next; d_reset[e] != 0: env e starts a new episode
+ *     with this row: ep_id[e] += 1, ep_step[e] = 0; otherwise ep_step[e] += 1 (the replay's own uint32 counters; the batch's episode books
+ *     are not read).  From PENDING it also closes the pending transition: pushed += 1.
+ *   record(d_ctrl [N,nu], d_next_obs [N,obs_dim], d_reward [N], d_done [N]): only from READY, after hsr_batch_step_dev and BEFORE
+ *     hsr_batch_episode_end_dev / any reset.  Writes slot pushed mod T of every env: obs = the committed row, act, next_obs, reward, done
+ *     (NULL: the flag the step latched, reward = float(flag), as in hsr_batch_episode_end_dev), ep_id, ep_step, achieved_next =
+ *     xpos(goal_body) as hsr_batch_body_xpos gives it for the step just run, desired = the env's mocap_pos.
+ *   clear: back to EMPTY, pushed = 0, counters 0; frees nothing.
+ * Sampling (the replacement of ReplayBuffer.sample, rl_utils/replay_buffer.py:64-82, with the 'future' relabelling strategy): count =
+ * min(pushed, T); the stored steps of an env have ages j = 0 .. count-1, oldest first, slot(j) = (pushed - count + j) mod T.  Sample i of
+ * draw `draw` takes the Philox block of key (seed & 0xffffffff, seed >> 32), counter (i, draw, 4, env_offset); mulhi(w, n) = (w n) >> 32:
+ *   e = mulhi(word0, N), j = mulhi(word1, count), relabel = (float)(word2 >> 8) 2^-24 < her_ratio (a float32 compare);
+ *   j_end = the largest age >= j with the ep_id of age j (ids are monotone per env: the run is contiguous);
+ *   j_goal = j + mulhi(word3, j_end - j + 1).
+ *   not relabelled: goal = desired[j], reward and done as stored;
+ *   relabelled: goal = achieved_next[j_goal], reward = float(norm(achieved_next[j] - goal) < geofence) - the env's own goal test,
+ *     hsr/env.py:124-133,137-147 -, done = reward != 0 (success is the only terminal; truncation never is).
+ *   obs / act / next_obs / achieved_next are the rows of (e, slot(j)) as stored, moved as 32-bit patterns;
+ *   d_index[i] = (e, slot(j), relabelled ? slot(j_goal) : -1, relabelled).
+ * Every output may be NULL.  The call is asynchronous and never writes the ring or the batch.  HSR_EINVAL: count == 0, a pending record,
+ * batch < 1, her_ratio not in [0, 1]. */
+typedef struct hsr_replay_spec {
+    uint64_t seed;
+    uint32_t env_offset;      /* as in hsr_episode_spec: salts the draws of a shard */
+    int32_t  capacity_steps;  /* T: env-steps kept per env (ring) */
+    int32_t  obs_dim;         /* floats per observation row the caller will hand over (nq+nv, or 25 for 'openai') */
+    int32_t  goal_body;       /* the body whose xpos is the achieved goal; not the mocap body */
+    float    geofence;
+} hsr_replay_spec;
+/* HSR_EINVAL (nothing allocated, the batch as it was): a NULL argument, capacity_steps < 1, obs_dim < 1 or above 2^20, a goal_body out of
+ * range or the mocap body, a geofence that is not finite or <= 0, a ring beyond 2^40 bytes, and a batch with extra goal terms
+ * (hsr_batch_set_goals with n > 0: a reward of several terms cannot be recomputed from one relabelled point; record refuses likewise when
+ * terms were set later).  HSR_EDEVICE: no device memory; what was allocated is freed. */
+int  hsr_batch_replay_create(hsr_batch *b, const hsr_replay_spec *spec, hsr_replay **out);
+void hsr_replay_destroy(hsr_replay *r);
+int  hsr_replay_clear(hsr_replay *r);
+int  hsr_replay_commit_dev(hsr_replay *r, const float *d_obs, const uint8_t *d_reset);
+int  hsr_replay_record_dev(hsr_replay *r, const float *d_ctrl, const float *d_next_obs, const float *d_reward, const uint8_t *d_done);
+int  hsr_replay_state(hsr_replay *r, int32_t *count, int32_t *head_slot, uint32_t *pushed_lo); /* host books, no device work: count, pushed mod T, pushed & 0xffffffff */
+int  hsr_replay_sample_dev(hsr_replay *r, uint32_t draw, int batch, float her_ratio,
+                           float *d_obs, float *d_act, float *d_next_obs, float *d_goal, float *d_achieved_next,
+                           float *d_reward, uint8_t *d_done, int32_t *d_index /*[batch,4]*/);
 
 /* diagnostics (meaningful only in the -DHSR_PHASE_TIMING build, libhsrsim_timing.so; tools/phase_timing.py,
  * tools/block_times.py): per-phase cycle sums of the last launches, and per-workgroup
