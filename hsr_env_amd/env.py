@@ -17,7 +17,9 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
+from .episodes import EpisodeSpec, ResetPlan
 from .model import Model, load_config
+from .sim import raise_if_diverged
 from .spaces import Box, Space
 
 GoalSpec = namedtuple("GoalSpec", "a b distance")     # hsr/env.py:20
@@ -93,8 +95,6 @@ class VecHSREnv:
             raise ValueError("max_episode_steps belongs to auto_reset=True (rl.TimeLimit wraps an env without it)")
         if self.auto_reset and not hasattr(sim, "set_episodes"):
             raise NotImplementedError("auto_reset=True needs a simulator handle with set_episodes (BatchSim): episodes run on the device")
-        self._dev = None
-        self._replay = None            # make_replay(): the hindsight replay the device loop feeds
         # hsr/env.py:50-66: record when any of record / record_path / record_freq is given.  One video per recorded env (global ids
         # record_envs, default [0]; a rank records the ones in its shard) under the directory record_path (record.py)
         self._recorder = None
@@ -115,8 +115,12 @@ class VecHSREnv:
         self.obs_dim = 25 if obs_type == "openai" else model.nq + model.nv
         high = np.inf * np.ones(self.obs_dim)
         self.observation_space = Box(-high, high, dtype=np.float32)
-        self._goal_body, self._geofence = -1, 0.0
+        self._loop = None              # device_loop.DeviceLoop: the torch side of auto_reset=True, which alone has one
+        if self.auto_reset:
+            from .device_loop import DeviceLoop
+            self._loop = DeviceLoop(sim, self.n_envs, model.nu, model.nq + model.nv, self.obs_dim)
         self._goal_points = np.zeros((self.n_envs, 3), dtype=np.float32)
+        self._plan = ResetPlan.from_env(model, self.starts, goals, block_space)      # what a reset samples and a step tests, parsed once
         self._parse_goals()
         self.seed()
         t, q, v = self.sim.get_state()
@@ -127,38 +131,46 @@ class VecHSREnv:
     def _squeeze(self, x):
         return x[0] if self.n_envs == 1 else x
 
+    def _scalar(self, x):
+        """A per-env value that the reference holds as a Python scalar."""
+        return x[0].item() if self.n_envs == 1 else x
+
+    def _count_step(self, done):
+        """Every env has taken one more step -> the success that is logged (hsr/env.py:133)."""
+        self._time_steps += 1
+        return done & (self._time_steps > 0)
+
+    def _step_result(self, obs, rew, done, success, ns, **episode_info):
+        """What step() returns; with n_envs == 1 in the reference's scalar shapes."""
+        self._last_obs = obs
+        info = {"log count": {"success": self._squeeze(success)}, "substeps": self._squeeze(ns), **episode_info}
+        return self._squeeze(obs), self._scalar(rew), self._scalar(done), info
+
+    def _mask(self, mask):
+        return np.ones(self.n_envs, dtype=bool) if mask is None else np.asarray(mask, dtype=bool).reshape(self.n_envs)
+
     def _parse_goals(self):
         """hsr/env.py:124-126,137-147: `done = all(in_range(a, b, d) for a, b, d in goals)`, an operand being a body name
         (its xpos), a point (ndarray, or a Space sampled at reset) or a callable.  On the device a goal is a pair of bodies, or a
         body and THE point: like the reference, whose reset writes the concatenation of all point operands into the single
         mocap_pos[1, 3] (hsr/env.py:169-172), at most one point operand can exist across the goals.  The goal that holds the
         point is the main term of hsr_batch_step (goal_body, geofence); body-body goals become the extra terms of
-        hsr_batch_set_goals (the mocap body stands for the point there).  Callables cannot run inside the substep loop."""
-        self._goal_body, self._geofence, self._point_goal, self._extra_terms = -1, 0.0, None, []
-        if not self.goals_specs:
-            return
-        mocap_body = next((i for i, mc in enumerate(self.model.arrays["body_mocap"]) if mc), None)
-        for gi, (a, b, d) in enumerate(self.goals_specs):
+        hsr_batch_set_goals (the mocap body stands for the point there).  Callables cannot run inside the substep loop.
+        The parse is episodes.ResetPlan; what this env refuses of it is here."""
+        for a, b, d in self.goals_specs or []:
             for x in (a, b):
                 if callable(x) and not isinstance(x, Space):
                     raise RuntimeError(f"{x} must be np.ndarray or string: callables cannot be evaluated inside the device substep loop")
                 if not isinstance(x, (str, np.ndarray, Space, list, tuple)):
                     raise RuntimeError(f"{x} must be function, np.ndarray, or string")      # hsr/env.py:145
-            points = [x for x in (a, b) if not isinstance(x, str)]
-            if len(points) == 2:
+            if not (isinstance(a, str) or isinstance(b, str)):
                 raise RuntimeError("a goal between two points does not depend on the simulation")
-            if points:
-                if self._point_goal is not None:
-                    raise ValueError("the goals hold more than one point operand: mocap_pos has room for one (hsr/env.py:169-172)")
-                body = a if isinstance(a, str) else b
-                self._point_goal, self._goal_body, self._geofence = gi, self.model.body_id(body), float(d)
-            else:
-                self._extra_terms.append((self.model.body_id(a), self.model.body_id(b), float(d)))
-        if len(self._extra_terms) > 4:
+        if len(self._plan.points) > 1:
+            raise ValueError("the goals hold more than one point operand: mocap_pos has room for one (hsr/env.py:169-172)")
+        if len(self._plan.extra_terms) > 4:
             raise NotImplementedError("at most four body-body goals besides the point goal")
-        if self._extra_terms and not hasattr(self.sim, "set_goals"):
+        if self._plan.extra_terms and not hasattr(self.sim, "set_goals"):
             raise NotImplementedError("this simulator handle does not evaluate body-body goals")
-        del mocap_body
 
     @property
     def dt(self):
@@ -168,11 +180,9 @@ class VecHSREnv:
         self._seed = 0 if seed is None else int(seed)
         self._reset_count = 0
         self.np_random = np.random.Generator(np.random.Philox(key=self._seed))
-        if self.auto_reset:                                             # the device sampler restarts: same seed, same run
-            from .episodes import EpisodeSpec
-            self.sim.set_episodes(EpisodeSpec.from_env(self.model, self.starts, self.goals_specs, self.block_space, seed=self._seed,
-                                                       env_offset=self.env_offset, max_episode_steps=self.max_episode_steps))
-            self._action_step = 0
+        if self._loop is not None:                                      # the device sampler restarts: same seed, same run
+            self._loop.restart(EpisodeSpec.from_plan(self.model, self._plan, seed=self._seed, env_offset=self.env_offset,
+                                                     max_episode_steps=self.max_episode_steps))
         return [seed]
 
     def _global_rng(self):
@@ -188,160 +198,73 @@ class VecHSREnv:
         """hsr/env.py:149-156: qpos with every joint in ``starts`` resampled (per env)."""
         rng = rng or self._global_rng()
         qpos = np.tile(self.model.qpos0, (self.n_global, 1))
-        for joint, space in self.starts.items():
+        for joint, start, end, space in self._plan.starts:
             assert isinstance(space, Space)
-            adr = self.model.joint_qpos_addr(joint)
-            start, end = adr if isinstance(adr, tuple) else (adr, adr + 1)
             qpos[:, start:end] = space.sample(self.n_global, rng=rng)
-        if self.block_space is not None:
-            nb = (self.model.nq - self.model.nu) // 7
-            for b in range(nb):
-                a = self.model.nu + 7 * b
-                qpos[:, a:a + 7] = block_space_to_qpos(self.block_space.sample(self.n_global, rng=rng))
+        for a in self._plan.block_qadr:
+            qpos[:, a:a + 7] = block_space_to_qpos(self._plan.block_space.sample(self.n_global, rng=rng))
         return self._shard(qpos)
 
-    def reset(self, mask=None):
-        """sim.reset() + reset_model() (hsr/mujoco_env.py:83-85, hsr/env.py:158-177); ``mask`` selects envs."""
-        if self.auto_reset:
-            return self._reset_sampled(mask)
-        rng = self._global_rng()
-        self._reset_count += 1
-        m = np.ones(self.n_envs, dtype=bool) if mask is None else np.asarray(mask, dtype=bool).reshape(self.n_envs)
+    def _sample_goal_points(self, m, rng):
+        """The host sampler's goal point for the envs `m`; the first draws of a reset's stream, before new_state()."""
+        pt = self._plan.point
+        if pt is None:
+            return
+        pts = pt.sample(self.n_global, rng=rng) if isinstance(pt, Space) else np.tile(np.asarray(pt, dtype=np.float32), (self.n_global, 1))
+        pts = self._shard(np.asarray(pts, dtype=np.float32).reshape(self.n_global, 3))
+        self._goal_points[m] = pts[m]
+
+    def _begin_episodes(self, m):
+        """The envs `m` start an episode: the recorder closes theirs and their step count restarts."""
         if self._recorder is not None:
             self._recorder.on_reset(m, self._time_steps > 0)
         self._time_steps[m] = 0
-        if self.goals_specs:
-            if self._extra_terms and self.goals is None:
-                self.sim.set_goals(self._extra_terms)               # from the first reset on (before it `goals is None`: hsr/env.py:39,125)
+
+    def _begin_goals(self):
+        """From the first reset() on the goals are tested (before it `goals is None`: hsr/env.py:39,125)."""
+        if self.goals_specs and self.goals is None:
+            if self._plan.extra_terms:
+                self.sim.set_goals(self._plan.extra_terms)
             self.goals = list(self.goals_specs)
-            if self._point_goal is not None:
-                a, b, d = self.goals_specs[self._point_goal]
-                pt = b if isinstance(a, str) else a
-                pts = pt.sample(self.n_global, rng=rng) if isinstance(pt, Space) else np.tile(np.asarray(pt, dtype=np.float32), (self.n_global, 1))
-                pts = self._shard(np.asarray(pts, dtype=np.float32).reshape(self.n_global, 3))
-                self._goal_points[m] = pts[m]
-                cur = self._squeeze(self._goal_points)
-                self.goals[self._point_goal] = GoalSpec(a, cur, d) if isinstance(a, str) else GoalSpec(cur, b, d)
+
+    def _refresh_goal_points(self):
+        """The goal points the device drew (its mocap_pos) -> ``goals`` / ``in_range``."""
+        if self._plan.point_goal is not None and self.goals is not None:
+            self._goal_points = np.asarray(self.sim.body_xpos(self._plan.mocap_body), dtype=np.float32)
+            self._publish_goal_points()
+
+    def _publish_goal_points(self):
+        """``goals`` holds the point goal with the current ``_goal_points``."""
+        gi = self._plan.point_goal
+        if gi is None or self.goals is None:
+            return
+        a, b, d = self.goals_specs[gi]
+        cur = self._squeeze(self._goal_points)
+        self.goals[gi] = GoalSpec(a, cur, d) if isinstance(a, str) else GoalSpec(cur, b, d)
+
+    def reset(self, mask=None):
+        """sim.reset() + reset_model() (hsr/mujoco_env.py:83-85, hsr/env.py:158-177); ``mask`` selects envs.  With auto_reset=True the
+        device draws the episodes (and the goal points this object then reads back)."""
+        m = self._mask(mask)
+        self._begin_episodes(m)
+        self._begin_goals()
+        if self._loop is not None:
+            self._loop.reset(m)
+            self._refresh_goal_points()
+            obs = self._get_observation()
+            self._loop.commit_host_rows(self._last_obs, m)
+            return obs
+        rng = self._global_rng()
+        self._reset_count += 1
+        self._sample_goal_points(m, rng)
+        self._publish_goal_points()
         qpos = self.new_state(rng).astype(np.float32)
         self.sim.reset(mask=m.astype(np.uint8), qpos0=qpos, mocap=self._goal_points)
         return self._get_observation()
 
-    # ------------------------------------------------------------------ episodes on the device (auto_reset=True)
-    def _begin_goals(self):
-        if self.goals_specs:
-            if self._extra_terms and self.goals is None:
-                self.sim.set_goals(self._extra_terms)
-            if self.goals is None:
-                self.goals = list(self.goals_specs)
-
-    def _refresh_goal_points(self):
-        """The goal points the device drew (its mocap_pos) -> ``goals`` / ``in_range``."""
-        if self._point_goal is None or self.goals is None:
-            return
-        mocap_body = next(i for i, mc in enumerate(self.model.arrays["body_mocap"]) if mc)
-        self._goal_points = np.asarray(self.sim.body_xpos(mocap_body), dtype=np.float32)
-        self._publish_goal_points()
-
-    def _publish_goal_points(self):
-        """``goals`` holds the point goal with the current ``_goal_points``."""
-        if self._point_goal is None or self.goals is None:
-            return
-        a, b, d = self.goals_specs[self._point_goal]
-        cur = self._squeeze(self._goal_points)
-        self.goals[self._point_goal] = GoalSpec(a, cur, d) if isinstance(a, str) else GoalSpec(cur, b, d)
-
-    def _reset_sampled(self, mask):
-        m = np.ones(self.n_envs, dtype=bool) if mask is None else np.asarray(mask, dtype=bool).reshape(self.n_envs)
-        if self._recorder is not None:
-            self._recorder.on_reset(m, self._time_steps > 0)
-        self._time_steps[m] = 0
-        self._begin_goals()
-        self.sim.reset_sampled(m)
-        self._refresh_goal_points()
-        obs = self._get_observation()
-        if self._replay is not None:
-            self._replay_commit_host(self._last_obs, m)
-        return obs
-
-    def _device_buffers(self):
-        """torch tensors on the batch's device and the batch's stream as a torch stream: what the device loop reads and writes."""
-        if self._dev is None:
-            import torch
-            dev = torch.device("cuda", getattr(self.sim, "device", 0))
-            n, no = self.n_envs, self.model.nq + self.model.nv
-            f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-            self._dev = dict(stream=torch.cuda.ExternalStream(self.sim.stream_ptr(), device=dev), ctrl=f32(n, self.model.nu), obs=f32(n, no),
-                             final=f32(n, no), rew=f32(n), fret=f32(n), done=torch.zeros(n, dtype=torch.uint8, device=dev),
-                             kind=torch.zeros(n, dtype=torch.uint8, device=dev), ns=torch.zeros(n, dtype=torch.int32, device=dev),
-                             flen=torch.zeros(n, dtype=torch.int32, device=dev))
-            if self._replay is not None:                                # rows handed to the replay that no other buffer holds
-                self._dev.update(robs=f32(n, self.obs_dim), rmask=torch.zeros(n, dtype=torch.uint8, device=dev))
-            torch.cuda.synchronize(dev)                                 # the fills ran on torch's stream, the batch has its own
-        return self._dev
-
     def sample_action_dev(self):
         """Uniform actions over the action space drawn on the device (torch float32 [n_envs, nu]); every call is the next action step."""
-        import torch
-        d = self._device_buffers()
-        with torch.cuda.stream(d["stream"]):
-            self.sim.sample_ctrl_dev(self._action_step, d["ctrl"].data_ptr())
-        self._action_step += 1
-        return d["ctrl"]
-
-    def _step_auto_reset(self, action, steps):
-        import torch
-        d = self._device_buffers()
-        goal_body = self._goal_body if self.goals else -1
-        with torch.cuda.stream(d["stream"]):
-            if isinstance(action, torch.Tensor):
-                if action.data_ptr() != d["ctrl"].data_ptr():
-                    d["ctrl"].copy_(action.reshape(self.n_envs, self.model.nu))
-            else:
-                d["ctrl"].copy_(torch.from_numpy(np.ascontiguousarray(action, dtype=np.float32).reshape(self.n_envs, self.model.nu)))
-            ptr = {k: v.data_ptr() for k, v in d.items() if k != "stream"}
-            self.sim.step_dev(ptr["ctrl"], steps, goal_body, self._geofence, ptr["obs"], ptr["rew"], ptr["done"], ptr["ns"])
-            bad, any_bad = self.sim.bad_state()
-            if any_bad:
-                from .sim import MujocoException
-                raise MujocoException(f"simulation diverged in env(s) {np.flatnonzero(bad)[:8].tolist()} (non-finite or |q| > 1e10)")
-            self._time_steps += 1
-            if self._recorder is not None:
-                self._recorder.after_step(d["done"].cpu().numpy().astype(bool), d["ns"].cpu().numpy())
-            final = self.sim.obs_openai() if self._obs_type == "openai" else None       # before the reset moves the bodies
-            if self._replay is not None:                                                # likewise: the achieved goal is read from the poses of this step
-                if final is not None:
-                    self.sim.obs_openai_dev(d["robs"].data_ptr())
-                self._replay.record(d["ctrl"], d["obs"] if final is None else d["robs"], d["rew"], d["done"])
-            self.sim.episode_end_dev(ptr["obs"], ptr["rew"], ptr["done"], ptr["final"] if final is None else None, ptr["kind"], ptr["fret"], ptr["flen"])
-            if self._replay is not None:
-                if final is not None:
-                    self.sim.obs_openai_dev(d["robs"].data_ptr())                       # the first observation of the envs that were reset
-                self._replay.commit(d["obs"] if final is None else d["robs"], d["kind"])
-            host = {k: d[k].cpu().numpy() for k in ("obs", "rew", "done", "ns", "kind", "fret", "flen")}
-            if final is None:
-                final = d["final"].cpu().numpy()
-        kind = host["kind"]
-        reset = kind != 0
-        if self._recorder is not None:
-            self._recorder.on_reset(reset, self._time_steps > 0)
-        success = host["done"].astype(bool)
-        info = {"log count": {"success": self._squeeze(success & (self._time_steps > 0))}, "substeps": self._squeeze(host["ns"]),
-                "terminal_observation": self._squeeze(final), "TimeLimit.truncated": self._squeeze(kind == 2),
-                "episode": {"r": self._squeeze(host["fret"]), "l": self._squeeze(host["flen"])}}
-        self._time_steps[reset] = 0
-        obs = host["obs"]
-        if reset.any():
-            self._refresh_goal_points()
-            if self._obs_type == "openai":
-                obs = self.sim.obs_openai()
-        elif self._obs_type == "openai":
-            obs = final
-        self._last_obs = obs
-        if self.n_envs == 1:
-            info["TimeLimit.truncated"] = bool(kind[0] == 2)
-            info["episode"] = {"r": float(host["fret"][0]), "l": int(host["flen"][0])}
-            return obs[0], float(host["rew"][0]), bool(reset[0]), info
-        return obs, host["rew"], reset, info
+        return self._loop.sample_action()
 
     # ------------------------------------------------------------------ hindsight replay on the device (replay.py; DESIGN.md)
     def make_replay(self, capacity_steps: int, her_ratio: float = 0.8, seed: Optional[int] = None):
@@ -349,39 +272,22 @@ class VecHSREnv:
         step and the episode end, so the achieved goal is the one of the step, not of the next episode's start) and commits the
         observation it returns, and reset() commits too; ``replay.sample(batch_size)`` then draws relabelled minibatches without a copy
         to the host.  Rows are this env's observations (25 floats with obs_type='openai').  seed None: the env's seed."""
-        if not self.auto_reset:
+        if self._loop is None:
             raise ValueError("make_replay needs auto_reset=True: the replay is fed by the device loop, which only that mode runs")
-        if self._point_goal is None:
+        if self._plan.point_goal is None:
             raise NotImplementedError("make_replay needs a point goal (a body and a point): hindsight relabelling replaces that point by a "
                                       "position the body reached")
-        if self._extra_terms:
+        if self._plan.extra_terms:
             raise NotImplementedError("make_replay with body-body goals besides the point goal: their reward cannot be recomputed from a relabelled point")
-        if self._replay is not None:
+        if self._loop.replay is not None:
             raise ValueError("this env already feeds a replay")
         from .replay import HindsightReplay
-        self._replay = HindsightReplay(self.sim, capacity_steps, self._goal_body, self._geofence, obs_dim=self.obs_dim, her_ratio=her_ratio,
-                                       seed=self._seed if seed is None else seed, env_offset=self.env_offset)
-        self._dev = None                                                # the buffers gain the replay's staging rows
+        replay = HindsightReplay(self.sim, capacity_steps, self._plan.goal_body, self._plan.geofence, obs_dim=self.obs_dim, her_ratio=her_ratio,
+                                 seed=self._seed if seed is None else seed, env_offset=self.env_offset)
+        self._loop.attach_replay(replay)
         self._get_observation()
-        self._replay_commit_host(self._last_obs, None)
-        return self._replay
-
-    def _replay_commit_host(self, obs, mask):
-        """commit() of host rows: the observation reset() returns, and the envs it began an episode for."""
-        import torch
-        d = self._device_buffers()
-        with torch.cuda.stream(d["stream"]):
-            d["robs"].copy_(torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32).reshape(self.n_envs, self.obs_dim)))
-            if mask is not None:
-                d["rmask"].copy_(torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.n_envs)))
-            self._replay.commit(d["robs"], None if mask is None else d["rmask"])
-            d["stream"].synchronize()                                   # the host rows are pageable: the copies must not outlive them
-
-    def _replay_restart(self):
-        """After a jump (load_state, fork) the ring describes a past the envs no longer have: forget it and start from the current rows."""
-        if self._replay is not None:
-            self._replay.clear()
-            self._replay_commit_host(self._last_obs, None)
+        self._loop.commit_host_rows(self._last_obs)
+        return replay
 
     # ------------------------------------------------------------------ exact snapshots (sim.Snapshot; DESIGN.md)
     def _no_jump_while_recording(self, what):
@@ -394,7 +300,7 @@ class VecHSREnv:
         self._no_jump_while_recording("save_state")
         snap = self.sim.snapshot()
         snap.save()
-        return EnvState(snap, self._time_steps.copy(), self._goal_points.copy(), self._reset_count, getattr(self, "_action_step", 0),
+        return EnvState(snap, self._time_steps.copy(), self._goal_points.copy(), self._reset_count, self._loop.action_step if self._loop is not None else 0,
                         self._last_obs.copy(), self.goals is not None)
 
     def load_state(self, state: EnvState):
@@ -407,11 +313,11 @@ class VecHSREnv:
         self._time_steps[:] = state.time_steps
         self._goal_points = state.goal_points.copy()
         self._reset_count = state.reset_count
-        if self.auto_reset:
-            self._action_step = state.action_step
         self._last_obs = state.last_obs.copy()
         self._publish_goal_points()
-        self._replay_restart()
+        if self._loop is not None:
+            self._loop.action_step = state.action_step
+            self._loop.restart_replay(self._last_obs)
 
     def fork(self, src, dst):
         """Envs `dst` become copies of env(s) `src` (one id for all, or one per destination), on the device, and continue bit for bit as
@@ -425,7 +331,8 @@ class VecHSREnv:
         self._goal_points[dst] = self._goal_points[src]
         self._last_obs[dst] = self._last_obs[src]
         self._publish_goal_points()
-        self._replay_restart()
+        if self._loop is not None:
+            self._loop.restart_replay(self._last_obs)
 
     def set_state(self, qpos, qvel):
         qpos = np.asarray(qpos, dtype=np.float32).reshape(self.n_envs, -1)
@@ -451,29 +358,30 @@ class VecHSREnv:
         info['TimeLimit.truncated'] and info['episode'] = {'r', 'l'} (valid where done) describe the episode that ended, and the
         returned rows of those envs are the first observation of their next episode.  `action` may then be a torch tensor on the device."""
         steps = steps or self.steps_per_action
-        if self.auto_reset:
-            return self._step_auto_reset(action, steps)
-        action = np.asarray(action, dtype=np.float32).reshape(self.n_envs, self.model.nu)
-        goal_body = self._goal_body if self.goals else -1
-
-        obs, rew, done, ns = self.sim.step(action, steps, goal_body, self._geofence)
-        bad_state = getattr(self.sim, "bad_state", None)
-        if bad_state is not None:
-            bad, any_bad = bad_state()
-            if any_bad:                                                 # mujoco_py.MujocoException on MuJoCo's divergence warnings
-                from .sim import MujocoException
-                raise MujocoException(f"simulation diverged in env(s) {np.flatnonzero(bad)[:8].tolist()} (non-finite or |q| > 1e10)")
-        self._time_steps += 1
-        if self._recorder is not None:
-            self._recorder.after_step(done, ns)
-        if self._obs_type == "openai":
-            obs = self.sim.obs_openai()
-        self._last_obs = obs
-        success = done
-        info = {"log count": {"success": self._squeeze(success & (self._time_steps > 0))}, "substeps": self._squeeze(ns)}
-        if self.n_envs == 1:
-            return obs[0], float(rew[0]), bool(done[0]), info
-        return obs, rew, done, info
+        goal_body = self._plan.goal_body if self.goals else -1
+        openai = self._obs_type == "openai"
+        if self._loop is None:
+            action = np.asarray(action, dtype=np.float32).reshape(self.n_envs, self.model.nu)
+            obs, rew, done, ns = self.sim.step(action, steps, goal_body, self._plan.geofence)
+            raise_if_diverged(self.sim)
+            success = self._count_step(done)
+            if self._recorder is not None:
+                self._recorder.after_step(done, ns)
+            if openai:
+                obs = self.sim.obs_openai()
+            return self._step_result(obs, rew, done, success, ns)
+        r = self._loop.step(action, steps, goal_body, self._plan.geofence, openai, self._recorder)
+        success = self._count_step(r.done.astype(bool))
+        reset = r.kind != 0
+        self._begin_episodes(reset)
+        if reset.any():
+            self._refresh_goal_points()
+        obs = r.obs
+        if openai:                                                      # no env was reset: the rows read before the episode end still hold
+            obs = self.sim.obs_openai() if reset.any() else r.terminal_obs
+        return self._step_result(obs, r.reward, reset, success, r.nsteps, **{
+            "terminal_observation": self._squeeze(r.terminal_obs), "TimeLimit.truncated": self._scalar(r.kind == 2),
+            "episode": {"r": self._scalar(r.fin_return), "l": self._scalar(r.fin_length)}})
 
     def in_range(self, a, b, distance):
         def parse(x):

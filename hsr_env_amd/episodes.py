@@ -1,15 +1,16 @@
 """Episodes on the device: the spec ``BatchSim.set_episodes`` uploads (include/hsrsim.h: hsr_episode_spec).
 
-``EpisodeSpec.from_env`` turns the arguments of ``VecHSREnv`` - ``starts``, the goals, ``block_space`` - into the range tables the
-device sampler draws from, with the joint-address and block-slot rules of ``VecHSREnv.new_state``: a joint in ``starts`` is sampled
-over its qpos slice, every other qpos entry keeps ``qpos0`` (lo == hi), and with ``block_space`` block b occupies
-``qpos[nu + 7 b : nu + 7 b + 7]``.  The draws themselves (Philox4x32-10, keyed by seed and global env id) are csrc/episode.h.
+``ResetPlan.from_env`` is the one parse of the arguments of ``VecHSREnv`` - ``starts``, the goals, ``block_space`` - into what a reset
+samples and what a step tests: a joint in ``starts`` is sampled over its qpos slice, every other qpos entry keeps ``qpos0``, with
+``block_space`` block b occupies ``qpos[nu + 7 b : nu + 7 b + 7]``, and at most one goal holds a point.  The host sampler
+(``VecHSREnv.new_state`` / ``reset``) reads the plan, and ``EpisodeSpec`` turns the same plan into the range tables the device sampler
+draws from (lo == hi where nothing is sampled).  The draws themselves (Philox4x32-10, keyed by seed and global env id) are csrc/episode.h.
 """
 from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 
@@ -38,6 +39,49 @@ def _bounded(space: Box, what: str):
 
 
 @dataclass
+class ResetPlan:
+    """What a reset samples and what a step tests, as addresses and ids of the model.  A parse, not a judge: what the env or the device
+    sampler cannot do with a plan (two points, an unbounded Box, ...) is refused by ``VecHSREnv`` and ``EpisodeSpec.from_plan``."""
+    starts: List[tuple]                     # (joint, start, end, space): the qpos slices of ``starts``, in the dict's order
+    block_qadr: List[int]                   # with block_space: the qpos address of every block's free joint
+    block_space: Optional[Box]
+    points: List[tuple]                     # (goal index, operand) of every goal operand that is not a body name
+    goal_body: int                          # the main term, (goal_body, geofence): the goal between a body and the point
+    geofence: float
+    extra_terms: List[tuple]                # (body a, body b, distance) of the goals between two bodies
+    mocap_body: Optional[int]               # the body that carries the point on the device
+
+    @classmethod
+    def from_env(cls, model: Model, starts: Optional[Dict[str, Box]] = None, goals=None, block_space: Optional[Box] = None) -> "ResetPlan":
+        slices = []
+        for joint, space in (starts or {}).items():
+            adr = model.joint_qpos_addr(joint)                      # ValueError for a joint the model does not have
+            start, end = adr if isinstance(adr, tuple) else (adr, adr + 1)
+            slices.append((joint, start, end, space))
+        qadr = [model.nu + 7 * b for b in range((model.nq - model.nu) // 7)] if block_space is not None else []
+        plan = cls(starts=slices, block_qadr=qadr, block_space=block_space, points=[], goal_body=-1, geofence=0.0, extra_terms=[],
+                   mocap_body=next((i for i, mc in enumerate(model.arrays["body_mocap"]) if mc), None))
+        for gi, (a, b, d) in enumerate(goals or []):
+            bodies = [x for x in (a, b) if isinstance(x, str)]
+            plan.points += [(gi, x) for x in (a, b) if not isinstance(x, str)]
+            if len(bodies) == 2:
+                plan.extra_terms.append((model.body_id(a), model.body_id(b), float(d)))
+            elif len(bodies) == 1 and plan.goal_body < 0:
+                plan.goal_body, plan.geofence = model.body_id(bodies[0]), float(d)
+        return plan
+
+    @property
+    def point_goal(self) -> Optional[int]:
+        """Which goal holds the point operand."""
+        return self.points[0][0] if self.points else None
+
+    @property
+    def point(self):
+        """The point operand: an array, or a Space to sample."""
+        return self.points[0][1] if self.points else None
+
+
+@dataclass
 class EpisodeSpec:
     seed: int
     env_offset: int
@@ -54,29 +98,30 @@ class EpisodeSpec:
     @classmethod
     def from_env(cls, model: Model, starts: Optional[Dict[str, Box]] = None, goals=None, block_space: Optional[Box] = None,
                  seed: int = 0, env_offset: int = 0, max_episode_steps: Optional[int] = None) -> "EpisodeSpec":
+        return cls.from_plan(model, ResetPlan.from_env(model, starts, goals, block_space), seed, env_offset, max_episode_steps)
+
+    @classmethod
+    def from_plan(cls, model: Model, plan: "ResetPlan", seed: int = 0, env_offset: int = 0,
+                  max_episode_steps: Optional[int] = None) -> "EpisodeSpec":
         qlo = np.asarray(model.qpos0, np.float32).copy()
         qhi = qlo.copy()
-        for joint, space in (starts or {}).items():
-            adr = model.joint_qpos_addr(joint)                      # ValueError for a joint the model does not have
-            start, end = adr if isinstance(adr, tuple) else (adr, adr + 1)
+        for joint, start, end, space in plan.starts:
             lo, hi = _bounded(space, f"starts[{joint!r}]")
             if lo.size != end - start:
                 raise ValueError(f"starts[{joint!r}]: a Box of {lo.size} values for a qpos slice of {end - start}")
             qlo[start:end], qhi[start:end] = lo, hi
         spec = cls(seed=int(seed) & (2 ** 64 - 1), env_offset=int(env_offset), max_episode_steps=int(max_episode_steps or 0),
                    qpos_lo=qlo, qpos_hi=qhi)
-        if block_space is not None:
-            lo, hi = _bounded(block_space, "block_space")
+        if plan.block_space is not None:
+            lo, hi = _bounded(plan.block_space, "block_space")
             if lo.size != 4:
                 raise ValueError("block_space is a Box(4): x, y, z, yaw")
-            nb = (model.nq - model.nu) // 7
-            spec.block_qadr = np.array([model.nu + 7 * b for b in range(nb)], np.int32)
+            spec.block_qadr = np.array(plan.block_qadr, np.int32)
             spec.block_lo, spec.block_hi = lo, hi
-        points = [x for g in (goals or []) for x in (g[0], g[1]) if not isinstance(x, str)]
-        if len(points) > 1:
+        if len(plan.points) > 1:
             raise ValueError("the goals hold more than one point operand: mocap_pos has room for one")
-        if points:
-            pt = points[0]
+        if plan.points:
+            pt = plan.point
             if isinstance(pt, Space):
                 lo, hi = _bounded(pt, "goal space")
             else:

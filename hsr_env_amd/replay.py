@@ -11,6 +11,9 @@ Plumbing only: the kernels are csrc/replay.h.  There is no CPU stand-in.
 """
 from __future__ import annotations
 
+import torch
+
+from .device_loop import batch_stream, zero_tensors
 from .sim import BatchSim, ReplaySpec
 
 
@@ -24,7 +27,6 @@ class HindsightReplay:
 
     def __init__(self, sim: BatchSim, capacity_steps: int, goal_body: int, geofence: float, obs_dim: int = None, her_ratio: float = 0.8,
                  seed: int = 0, env_offset: int = 0):
-        import torch
         if not 0.0 <= float(her_ratio) <= 1.0:
             raise ValueError("her_ratio must lie in [0, 1]")
         self.sim, self.her_ratio = sim, float(her_ratio)
@@ -32,8 +34,7 @@ class HindsightReplay:
         spec = ReplaySpec(seed=int(seed) & (2 ** 64 - 1), env_offset=int(env_offset) & 0xffffffff, capacity_steps=self.capacity_steps,
                           obs_dim=self.obs_dim, goal_body=int(goal_body), geofence=float(geofence))
         self._replay = sim.replay(spec)
-        self._device = torch.device("cuda", getattr(sim, "device", 0))
-        self._stream = torch.cuda.ExternalStream(sim.stream_ptr(), device=self._device)
+        self._device, self._stream = batch_stream(sim)
         self._buffers = {}             # batch size -> the output tensors, allocated once
         self._draw = 0
 
@@ -57,16 +58,13 @@ class HindsightReplay:
         """The next minibatch: obs [B, obs_dim], action [B, nu], next_obs, goal [B, 3], achieved_next [B, 3], reward [B] (float32), done [B]
         (uint8) and index [B, 4] (int32: env, slot, goal slot or -1, relabelled), written on the batch's stream into tensors that the next
         sample() of the same size overwrites.  Order torch work after it with ``torch.cuda.stream(replay.stream)`` or a stream wait."""
-        import torch
         b = int(batch_size)
         out = self._buffers.get(b)
         if out is None:
-            f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self._device)
-            out = dict(obs=f32(b, self.obs_dim), action=f32(b, self.sim.nu), next_obs=f32(b, self.obs_dim), goal=f32(b, 3), achieved_next=f32(b, 3),
-                       reward=f32(b), done=torch.zeros(b, dtype=torch.uint8, device=self._device),
-                       index=torch.zeros((b, 4), dtype=torch.int32, device=self._device))
-            torch.cuda.synchronize(self._device)       # the fills ran on torch's stream, the batch has its own
-            self._buffers[b] = out
+            f32 = torch.float32
+            out = self._buffers[b] = zero_tensors(self._device, dict(
+                obs=((b, self.obs_dim), f32), action=((b, self.sim.nu), f32), next_obs=((b, self.obs_dim), f32), goal=((b, 3), f32),
+                achieved_next=((b, 3), f32), reward=((b,), f32), done=((b,), torch.uint8), index=((b, 4), torch.int32)))
         p = {k: v.data_ptr() for k, v in out.items()}
         self._replay.sample_dev(self._draw, b, self.her_ratio, p["obs"], p["action"], p["next_obs"], p["goal"], p["achieved_next"], p["reward"],
                                 p["done"], p["index"])

@@ -28,6 +28,15 @@ class MujocoException(RuntimeError):
     """Some env reached a non-finite state (reference: mujoco_py.MujocoException on MuJoCo warnings)."""
 
 
+def raise_if_diverged(sim):
+    """MujocoException when the last step left some env of `sim` non-finite (a handle without bad_state is not asked)."""
+    bad_state = getattr(sim, "bad_state", None)
+    if bad_state is not None:
+        bad, any_bad = bad_state()
+        if any_bad:                                                     # mujoco_py.MujocoException on MuJoCo's divergence warnings
+            raise MujocoException(f"simulation diverged in env(s) {np.flatnonzero(bad)[:8].tolist()} (non-finite or |q| > 1e10)")
+
+
 _vp, _fp_t, _u8p, _i32p = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
 _ip, _ullp = C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)
 _int, _float = C.c_int, C.c_float

@@ -240,3 +240,120 @@ def test_readme_command_line_selects_baseline_config_1(models):
     util.env_wrapper(lambda env_args, **kw: got.update(env_args))(**args)
     assert got["steps_per_action"] == 300 and got["goals"] is None and got["block_space"] is None
     assert got["model"].nv == 2 and got["model"].nu == 2 and not got["model"].block_body()
+
+
+# ------------------------------------------------------------------ the rules of auto_reset=True, on a scripted device loop
+class EpisodeStandIn(OracleBatchSim):
+    """The stand-in with an episode layer that does nothing: the scripted loop below says which envs were reset."""
+
+    def set_episodes(self, spec):
+        pass
+
+    def reset_sampled(self, mask=None):
+        pass
+
+    def move_goal(self, point):
+        self.reset(mocap=np.tile(np.float32(point), (self.n, 1)))
+
+
+class ScriptedLoop:
+    """In place of device_loop.DeviceLoop: step() hands out prepared records and, as DeviceLoop.step does between the step and the
+    episode end, tells the recorder what the step latched."""
+    replay = None
+
+    def __init__(self, sim, records):
+        self.sim, self.records = sim, list(records)
+
+    def reset(self, mask):
+        pass
+
+    def commit_host_rows(self, obs, mask=None):
+        pass
+
+    def step(self, action, steps, goal_body, geofence, openai, recorder):
+        r = self.records.pop(0)
+        self.sim.last = (r.nsteps, steps)                  # what FakeCaptureSim.step leaves for its capture calls
+        self.sim.steps = getattr(self.sim, "steps", 0) + 1
+        if recorder is not None:
+            recorder.after_step(r.done.astype(bool), r.nsteps)
+        return r
+
+
+def scripted_records(n, dim, steps=20):
+    from hsr_env_amd.device_loop import StepRecord
+    rng = np.random.default_rng(5)
+    kinds = np.array([[0, 0, 0], [1, 0, 2], [2, 1, 0]], np.uint8)[:, :n]       # env 0 alone meets 0, 1 and 2
+    return [StepRecord(obs=rng.random((n, dim), np.float32), reward=rng.random(n, np.float32), done=(k == 1).astype(np.uint8),
+                       nsteps=np.where(k == 1, 1, steps).astype(np.int32), kind=k, fin_return=rng.random(n, np.float32),
+                       fin_length=rng.integers(1, 3, n).astype(np.int32), terminal_obs=rng.random((n, dim), np.float32)) for k in kinds]
+
+
+@pytest.mark.parametrize("n", [3, 1])
+def test_auto_reset_rules_on_a_scripted_loop(models, n):
+    """What step() promises with auto_reset=True, without the device: done = done | truncated, the episode infos, the step counts,
+    goal points read back only after a reset, and the reference's scalar shapes with one env."""
+    m = models["cfg2"]
+    sim = EpisodeStandIn(m, n)
+    env = VecHSREnv(model=m, n_envs=n, sim=sim, goals=[GoalSpec("block0", Box(low=[-.1, -.2, .422], high=[.1, .2, .422]), .05)],
+                    steps_per_action=20, auto_reset=True, max_episode_steps=2)
+    records = scripted_records(n, m.nq + m.nv)
+    env._loop = ScriptedLoop(sim, records)
+    sim.move_goal([.01, .02, .422])
+    env.reset()
+    assert np.array_equal(env._goal_points, np.tile(np.float32([.01, .02, .422]), (n, 1))) and not env._time_steps.any()
+    sq = (lambda x: x[0]) if n == 1 else (lambda x: x)
+    count, points = np.zeros(n, np.int64), env._goal_points.copy()
+    for k, r in enumerate(records):
+        sim.move_goal([.03 + .01 * k, 0, .422])                 # what the device would have drawn for the envs it reset
+        obs, rew, done, info = env.step(np.zeros((n, m.nu)))
+        assert np.array_equal(obs, sq(r.obs)) and np.array_equal(rew, sq(r.reward))
+        assert np.array_equal(done, sq(r.kind != 0))
+        assert np.array_equal(info["TimeLimit.truncated"], sq(r.kind == 2))
+        assert np.array_equal(info["episode"]["r"], sq(r.fin_return)) and np.array_equal(info["episode"]["l"], sq(r.fin_length))
+        assert np.array_equal(info["terminal_observation"], sq(r.terminal_obs))
+        count = np.where(r.kind != 0, 0, count + 1)
+        assert np.array_equal(env._time_steps, count)
+        if (r.kind != 0).any():
+            points = np.tile(np.float32([.03 + .01 * k, 0, .422]), (n, 1))
+        assert np.array_equal(env._goal_points, points) and np.array_equal(env.goals[0].b, sq(points))
+        if n == 1:
+            assert obs.shape == (m.nq + m.nv,) and type(rew) is float and type(done) is bool
+            assert type(info["TimeLimit.truncated"]) is bool and type(info["episode"]["r"]) is float and type(info["episode"]["l"]) is int
+    assert np.array_equal(points[0], np.float32([.05, 0, .422]))       # the first record resets nobody, the other two do
+
+
+def test_auto_reset_tells_the_recorder_each_step_then_each_reset(models, tmp_path):
+    """record=True with auto_reset=True: per step one after_step with what the step latched, then one on_reset with the envs whose
+    episode ended; the video counts its episodes by them."""
+    import json
+    from test_record_host import FakeCaptureSim
+
+    class Sim(FakeCaptureSim):
+        set_episodes = reset_sampled = lambda self, arg=None: None
+
+        def body_xpos(self, body_id):
+            return np.zeros((self.n, 3), np.float32)
+
+    m, n = models["cfg2"], 3
+    sim = Sim(m, n)
+    env = VecHSREnv(model=m, n_envs=n, sim=sim, goals=[GoalSpec("block0", np.array([.4, 0, .422]), .05)], steps_per_action=20,
+                    auto_reset=True, max_episode_steps=2, record=True, record_path=tmp_path, record_size=(8, 6), record_camera=object())
+    records = scripted_records(n, m.nq + m.nv)
+    env._loop = ScriptedLoop(sim, records)
+    calls = []
+    for name in ("after_step", "on_reset"):
+        def spy(*args, _name=name, _call=getattr(env._recorder, name)):
+            calls.append((_name,) + tuple(np.array(a) for a in args))
+            return _call(*args)
+        setattr(env._recorder, name, spy)
+    env.reset()
+    assert [c[0] for c in calls] == ["on_reset"] and calls[0][1].all() and not calls[0][2].any()
+    for r in records:
+        del calls[:]
+        env.step(np.zeros((n, m.nu)))
+        assert [c[0] for c in calls] == ["after_step", "on_reset"]
+        assert np.array_equal(calls[0][1], r.done.astype(bool)) and np.array_equal(calls[0][2], r.nsteps)
+        assert np.array_equal(calls[1][1], r.kind != 0) and calls[1][2].all()
+    env.close()
+    frames = json.loads((tmp_path / "env0.meta.json").read_text())["frames"]      # env 0: goes on, done (1 substep, 50 tail frames), out of time
+    assert [(f["step"], f["episode"], f["tail"]) for f in frames] == [(0, 0, False)] + [(1, 0, False)] + [(1, 0, True)] * 50 + [(2, 1, False)]
