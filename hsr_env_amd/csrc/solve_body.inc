@@ -659,15 +659,19 @@
 #pragma unroll
                 for (int j = 0; j < 6; j++) cz_g[j] = o.g[j];
             }
-            if (!REP && CZG && c < KJ) {          // jt_force reads g out of this lane's registers; the wrench slots carry the row weights for hess_cached
-                cr[C2_FW] = o.dw[0]; cr[C2_FW + 1] = o.dw[1]; cr[C2_FW + 2] = o.dw[2]; cr[C2_TW] = o.dw[3]; cr[C2_TW + 1] = o.dw[4]; cr[C2_TW + 2] = o.dw[5];
-            } else if (!REP && c < KJ) {          // read back through the cached Jacobian entries (jt_force)
-                cr[C2_FW] = o.g[0]; cr[C2_FW + 1] = o.g[1]; cr[C2_FW + 2] = o.g[2]; cr[C2_TW] = o.g[3]; cr[C2_TW + 1] = o.g[4]; cr[C2_TW + 2] = o.g[5];
-            } else {
+            auto world_wrench = [&]() {
                 const v3 nn = mk3(cr[C2_N], cr[C2_N + 1], cr[C2_N + 2]), t1 = mk3(cr[C2_T1], cr[C2_T1 + 1], cr[C2_T1 + 2]), t2 = mk3(cr[C2_T2], cr[C2_T2 + 1], cr[C2_T2 + 2]);
                 const v3 fw = nn * o.g[0] + t1 * o.g[1] + t2 * o.g[2], tw = nn * o.g[3] + t1 * o.g[4] + t2 * o.g[5];
                 cr[C2_FW] = fw.x; cr[C2_FW + 1] = fw.y; cr[C2_FW + 2] = fw.z; cr[C2_TW] = tw.x; cr[C2_TW + 1] = tw.y; cr[C2_TW + 2] = tw.z;
-            }
+            };
+            if constexpr (!REP && CZG) {          // jt_force reads g out of this lane's registers; the wrench slots carry the row weights for hess_cached
+                // stored by EVERY contact lane, out of the registers the selects left them in, and overwritten by the lanes c >= KJ: one store for both kinds of
+                // lane behind the branch had the weights and the wrench merged into a third set of registers first (six copies per evaluation)
+                cr[C2_FW] = o.dw[0]; cr[C2_FW + 1] = o.dw[1]; cr[C2_FW + 2] = o.dw[2]; cr[C2_TW] = o.dw[3]; cr[C2_TW + 1] = o.dw[4]; cr[C2_TW + 2] = o.dw[5];
+                if (c >= KJ) world_wrench();
+            } else if (!REP && c < KJ) {          // read back through the cached Jacobian entries (jt_force)
+                cr[C2_FW] = o.g[0]; cr[C2_FW + 1] = o.g[1]; cr[C2_FW + 2] = o.g[2]; cr[C2_TW] = o.g[3]; cr[C2_TW + 1] = o.g[4]; cr[C2_TW + 2] = o.g[5];
+            } else world_wrench();
 #pragma unroll
             for (int j = 0; j < 6; j++) { cr[C2_GN + j] = o.gn[j]; cr[C2_U + j] = o.u[j]; }
             if (REP || !(CZG && c < KJ)) store_rows(rDw, adr, dim, o.dw);
@@ -965,7 +969,11 @@
                 { const int zc = (c < ncon) ? (int)con[C2_SIZE * c + C2_ZONE] : -1;
                   dc_[3] += (unsigned long long)ncw | ((unsigned long long)__popcll(__ballot(active && zc == 1)) << 20) | ((unsigned long long)__popcll(__ballot(active && zc == 2)) << 40); }
 #endif
-                static_for<0, KJ>([&](auto cc) { if (decltype(cc)::value < ncw) hess_cached(Hrow, cc, with_neg); });
+                // contact 0 is not behind `0 < ncw`: the chain's first matrix-core product then takes the cleared accumulator as a literal zero, where sixteen
+                // zeroed registers were merged with the chain's result across that test (16 copies per Hessian).  A wave without contacts (ncw = 0) adds
+                // record 0 with zero weights - or whatever it holds - into an accumulator that nothing reads: add_rows below keeps its test
+                if constexpr (KJ > 0) hess_cached(Hrow, std::integral_constant<int, 0>{}, with_neg);
+                static_for<(KJ > 0 ? 1 : 0), KJ>([&](auto cc) { if (decltype(cc)::value < ncw) hess_cached(Hrow, cc, with_neg); });
                 PHASE_S(7, 27);
                 for (int ci = KJ; ci < ncw; ci++) hess_contact(Hrow, ci, rDw, with_neg, active);
                 PHASE_S(7, 28);

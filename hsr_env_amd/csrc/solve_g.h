@@ -542,6 +542,9 @@ template <int G, int NK, int ND> __device__ __forceinline__ bool chol_g_tail(flo
     if (c >= ND) invd = __builtin_amdgcn_rsqf(diag);
     return chol_pivots_ok<G>(invd);
 }
+// whatever a register holds, at the price of no instruction: for the arm of a select that is never taken.  (An empty asm statement that "writes" v: the
+// value is defined, unlike an uninitialised variable; volatile so that two of them are never folded into one register that then had to be copied.)
+__device__ __forceinline__ float unspecified_value() { float v; asm volatile("" : "=v"(v)); return v; }
 // elliptic cone at residual x: cost, gradient g, and the Hessian in the form
 //   H = diag(dw) + Dm gn gn^T - k3 u u^T      (zone 0 top: all zero; 1 bottom: dw = D; 2 middle; k3 and u only mean something as this product)
 // The three cone functions take their six rows ZERO-PADDED: D[j] = x[j] = v[j] = 0 and fri[j - 1] = 0 for the rows j >= dim a contact
@@ -549,40 +552,64 @@ template <int G, int NK, int ND> __device__ __forceinline__ bool chol_g_tail(flo
 // (six exec-mask branches per call) is needed.
 struct ConeOut { float cost, Dm, k3; int zone; float g[6], dw[6], gn[6], u[6]; };
 __device__ __forceinline__ void cone_eval2(int /*dim*/, float mu, const float *fri, const float *D, const float *x, ConeOut &o) {
+    // No output is merged across a branch: a struct zeroed first and filled per zone behind early returns cost one register copy per field and
+    // arm (74 per evaluation, in a wave that is alone on its SIMD an issue slot each).  The zone is decided first, as lane predicates (ls_eval
+    // of solve_body.inc does the same); the bottom zone's two dozen instructions run for every lane, the middle zone's 75 behind ONE
+    // wave-uniform test (a resting wave has no lane there), and every field is formed once, by select.
     float U[6], T2 = 0;
-#pragma unroll
-    for (int j = 0; j < 6; j++) { o.g[j] = 0; o.dw[j] = 0; o.gn[j] = 0; o.u[j] = 0; }
-    o.cost = 0; o.Dm = 0; o.k3 = 0; o.zone = 0;
     U[0] = x[0] * mu;
     const float Nn = U[0];
 #pragma unroll
     for (int j = 1; j < 6; j++) { U[j] = x[j] * fri[j - 1]; T2 += U[j] * U[j]; }
     const float T = fsqrt(T2);
-    if (Nn >= mu * T || (T <= 0 && Nn >= 0)) return;
-    if (mu * Nn + T <= 0 || (T <= 0 && Nn < 0)) {
-        o.zone = 1;
+    // mu T ROUNDED, in the test and in NT below: the early-return form had the product in the block of the first test and the subtraction in the
+    // middle zone's, where no fma could be contracted from them; here they share a block, and fma(-mu, T, Nn) would be another number
+    float muT = mu * T;
+    asm("" : "+v"(muT));
+    const bool tz = T <= 0;
+    const bool top = (Nn >= muT) | (tz & (Nn >= 0));
+    const bool bot = !top & ((mu * Nn + T <= 0) | (tz & (Nn < 0)));
+    const bool mid = !(top | bot);
+    float cb = 0, gb[6];
 #pragma unroll
-        for (int j = 0; j < 6; j++) { o.cost += 0.5f * D[j] * x[j] * x[j]; o.g[j] = D[j] * x[j]; o.dw[j] = D[j]; }
-        return;
+    for (int j = 0; j < 6; j++) { cb += 0.5f * D[j] * x[j] * x[j]; gb[j] = D[j] * x[j]; }
+    // the middle zone's values.  Where the wave has no lane there they are never selected and are left unspecified - whatever the registers
+    // hold, no instruction - so the skipped arm has nothing to merge either; k3 and u, which are zero outside the zone and have no third
+    // value, are selected in the arm and are literal zeros without it.  (T = 0 is top or bottom: its infinities are never selected)
+    float Dm, k3, cm, gm[6], gn[6], um[6], dwm[6];
+    if (wave_any(mid)) {
+        const float NT = Nn - muT, invT = frcp(T);
+        Dm = D[0] * frcp(mu * mu * (1 + mu * mu));
+        const float kappa = -Dm * NT * mu;
+        // k3 = kappa / T^3 leaves the float range long before T^2 does (Dm mu^2 / T^2: T < 1e-16 with D = 1e6) while k3 u u^T stays of the order of Dm mu^2:
+        // below T^2 = 2^-64 the pair is kept as (k3 2^-80, u 2^40) - the same product, powers of two, so nothing is rounded; above, the factors are 1
+        const bool tiny = T2 < 0x1p-64f;
+        const float us = tiny ? 0x1p40f : 1.f, ts = tiny ? 0x1p80f : 1.f;
+        k3 = mid ? kappa * invT * frcp(T2 * ts) : 0.f;
+#pragma unroll
+        for (int j = 1; j < 6; j++) {
+            gn[j] = -mu * U[j] * fri[j - 1] * invT;
+            um[j] = mid ? fri[j - 1] * U[j] * us : 0.f;
+            dwm[j] = kappa * fri[j - 1] * fri[j - 1] * invT;
+        }
+#pragma unroll
+        for (int j = 0; j < 6; j++) gm[j] = Dm * NT * (j > 0 ? gn[j] : mu);
+        cm = 0.5f * Dm * NT * NT;
+    } else {
+        Dm = unspecified_value(); k3 = 0.f; cm = unspecified_value();
+#pragma unroll
+        for (int j = 0; j < 6; j++) { gm[j] = unspecified_value(); if (j > 0) gn[j] = unspecified_value(); um[j] = 0.f; dwm[j] = unspecified_value(); }
     }
-    o.zone = 2;
-    const float Dm = D[0] * frcp(mu * mu * (1 + mu * mu)), NT = Nn - mu * T, invT = frcp(T);
-    const float kappa = -Dm * NT * mu;
-    // k3 = kappa / T^3 leaves the float range long before T^2 does (Dm mu^2 / T^2: T < 1e-16 with D = 1e6) while k3 u u^T stays of the order of Dm mu^2:
-    // below T^2 = 2^-64 the pair is kept as (k3 2^-80, u 2^40) - the same product, powers of two, so nothing is rounded; above, the factors are 1
-    const bool tiny = T2 < 0x1p-64f;
-    const float us = tiny ? 0x1p40f : 1.f, ts = tiny ? 0x1p80f : 1.f;
-    o.Dm = Dm; o.k3 = kappa * invT * frcp(T2 * ts);
-    o.gn[0] = mu;
+    o.zone = top ? 0 : (bot ? 1 : 2);
+    o.cost = top ? 0.f : (bot ? cb : cm);
+    o.Dm = mid ? Dm : 0.f; o.k3 = k3;
 #pragma unroll
-    for (int j = 1; j < 6; j++) {
-        o.gn[j] = -mu * U[j] * fri[j - 1] * invT;
-        o.u[j] = fri[j - 1] * U[j] * us;
-        o.dw[j] = kappa * fri[j - 1] * fri[j - 1] * invT;
+    for (int j = 0; j < 6; j++) {
+        o.g[j] = top ? 0.f : (bot ? gb[j] : gm[j]);
+        o.dw[j] = top ? 0.f : (bot ? D[j] : (j > 0 ? dwm[j] : 0.f));
+        o.gn[j] = mid ? (j > 0 ? gn[j] : mu) : 0.f;
+        o.u[j] = j > 0 ? um[j] : 0.f;
     }
-#pragma unroll
-    for (int j = 0; j < 6; j++) o.g[j] = Dm * NT * o.gn[j];
-    o.cost = 0.5f * Dm * NT * NT;
 }
 
 // cost only (the warm-start comparison needs nothing else at the unconstrained point)
