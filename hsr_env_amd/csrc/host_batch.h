@@ -97,9 +97,12 @@ struct hsr_batch {
     bool snap_tab_built = false;   // snap_table checks the episode books' pointers in it against the batch's on every use
     // hindsight replays (host_replay.h) this batch made and nobody destroyed yet: hsr_batch_destroy releases their storage
     std::vector<hsr_replay *> replays;
+    // on-policy rollouts (host_rollout.h), likewise
+    std::vector<hsr_rollout *> rollouts;
 };
 static void snap_release_all(hsr_batch *b);     // host_snapshot.h
 static void replay_release_all(hsr_batch *b);   // host_replay.h
+static void rollout_release_all(hsr_batch *b);  // host_rollout.h
 template <typename T>
 static int dalloc(hsr_batch *b, T **p, size_t count) {
     void *q = nullptr;

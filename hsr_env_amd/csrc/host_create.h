@@ -435,6 +435,7 @@ extern "C" void hsr_batch_destroy(hsr_batch *b) {
     for (auto &kv : b->graphs) hipGraphExecDestroy(kv.second);
     snap_release_all(b);
     replay_release_all(b);
+    rollout_release_all(b);
     for (void *p : b->allocs) hipFree(p);
     if (b->d_rimg) hipFree(b->d_rimg);
     if (b->d_cap) hipFree(b->d_cap);

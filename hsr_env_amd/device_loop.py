@@ -1,8 +1,9 @@
 """The device loop of ``VecHSREnv(auto_reset=True)``: the torch and device-pointer plumbing around ``BatchSim``'s ``*_dev`` calls.
 
 ``DeviceLoop`` owns the batch's stream as a torch stream, the tensors a step reads and writes, the action-step counter of the device's
-action sampler and the attached ``replay.HindsightReplay``.  ``DeviceLoop.step`` is the one place where the order of the library calls
-of an env-step - step, record, episode end, commit - is written.  The env keeps the gym surface and the host books.
+action sampler and the attached ``replay.HindsightReplay`` and ``rollout.OnPolicyRollout`` (either, both or none; they do not know of each
+other).  ``DeviceLoop.step`` is the one place where the order of the library calls of an env-step - step, record, episode end, commit,
+close - is written.  The env keeps the gym surface and the host books.
 
 Importing this module imports torch; ``VecHSREnv`` does so only with ``auto_reset=True``.  There is no CPU stand-in.
 """
@@ -34,19 +35,25 @@ def zero_tensors(device, table):
 
 
 class DeviceLoop:
-    def __init__(self, sim, n_envs: int, nu: int, state_dim: int, obs_dim: int):
+    def __init__(self, sim, n_envs: int, nu: int, state_dim: int, obs_dim: int, openai: bool = False):
         self.sim, self.n, self.nu, self.state_dim, self.obs_dim = sim, n_envs, nu, state_dim, obs_dim
+        self.openai = bool(openai)     # the env's rows are the 25-float observation, which no step output holds
         self.action_step = 0           # the next draw of sample_action(); part of an env's saved state
         self.replay = None
-        self._buf = None               # the stream and the tensors, made at the first use (and again when a replay is attached)
+        self.rollout = None
+        self._buf = None               # the stream and the tensors, made at the first use (and again when a replay or rollout is attached)
 
     def _buffers(self):
         if self._buf is None:
             n, f32, u8, i32 = self.n, torch.float32, torch.uint8, torch.int32
             table = dict(ctrl=((n, self.nu), f32), obs=((n, self.state_dim), f32), final=((n, self.state_dim), f32), rew=((n,), f32),
                          fret=((n,), f32), done=((n,), u8), kind=((n,), u8), ns=((n,), i32), flen=((n,), i32))
-            if self.replay is not None:                                 # rows handed to the replay that no other buffer holds
+            # rows handed to the replay and the rollout that no other buffer holds: the policy rows (robs: the observation as the env
+            # returns it; with the state observation `obs` serves the rollout) and, for the 25-float observation, the terminal rows
+            if self.replay is not None or (self.rollout is not None and self.openai):
                 table.update(robs=((n, self.obs_dim), f32), rmask=((n,), u8))
+            if self.rollout is not None and self.openai:
+                table.update(rterm=((n, self.obs_dim), f32))
             device, stream = batch_stream(self.sim)
             self._buf = stream, zero_tensors(device, table)
         return self._buf
@@ -71,7 +78,9 @@ class DeviceLoop:
     def step(self, action, steps, goal_body, geofence, openai, recorder) -> StepRecord:
         """One env-step with the episode end inside it.  ``action``: host rows, or a torch tensor on the device (the tensor of
         sample_action() is used in place)."""
-        sim, replay = self.sim, self.replay
+        sim, replay, rollout = self.sim, self.replay, self.rollout
+        if rollout is not None and not rollout.staged:
+            raise ValueError("step() of an env that feeds a rollout needs rollout.stage(action, logp, value) first: the step would be lost to it")
         stream, d = self._buffers()
         ptr = {k: v.data_ptr() for k, v in d.items()}
         with torch.cuda.stream(stream):
@@ -85,15 +94,19 @@ class DeviceLoop:
                 recorder.after_step(d["done"].cpu().numpy().astype(bool), d["ns"].cpu().numpy())
             # before the reset moves the bodies: the terminal rows, and the achieved goal the replay reads from the poses of this step
             terminal = sim.obs_openai() if openai else None
+            fed = replay is not None or rollout is not None
+            term_rows, policy_rows = (d["rterm" if rollout is not None else "robs"], d["robs"]) if openai and fed else (d["final"], d["obs"])
+            if openai and fed:
+                sim.obs_openai_dev(term_rows.data_ptr())
             if replay is not None:
-                if openai:
-                    sim.obs_openai_dev(ptr["robs"])
-                replay.record(d["ctrl"], d["robs"] if openai else d["obs"], d["rew"], d["done"])
+                replay.record(d["ctrl"], term_rows if openai else d["obs"], d["rew"], d["done"])
             sim.episode_end_dev(ptr["obs"], ptr["rew"], ptr["done"], None if openai else ptr["final"], ptr["kind"], ptr["fret"], ptr["flen"])
+            if openai and fed:
+                sim.obs_openai_dev(policy_rows.data_ptr())              # the first observation of the envs that were reset
             if replay is not None:
-                if openai:
-                    sim.obs_openai_dev(ptr["robs"])                     # the first observation of the envs that were reset
-                replay.commit(d["robs"] if openai else d["obs"], d["kind"])
+                replay.commit(policy_rows, d["kind"])
+            if rollout is not None:                                     # after the replay's commit; neither reads what the other wrote
+                rollout.close_step(d["rew"], d["kind"], policy_rows, term_rows)
             host = {k: d[k].cpu().numpy() for k in ("obs", "rew", "done", "ns", "kind", "fret", "flen")}
             if not openai:
                 terminal = d["final"].cpu().numpy()
@@ -105,7 +118,9 @@ class DeviceLoop:
         self._buf = None                                                # the buffers gain the replay's staging rows
 
     def commit_host_rows(self, obs, mask=None):
-        """commit() of host rows: the observation reset() returns, and the envs it began an episode for (None: all of them)."""
+        """The host rows of a reset() - the observation it returns, and the envs it began an episode for (None: all of them) - go to what the
+        loop feeds: the replay commits them, the rollout begins again from them."""
+        self.begin_rollout(obs)
         if self.replay is None:
             return
         stream, d = self._buffers()
@@ -117,7 +132,25 @@ class DeviceLoop:
             stream.synchronize()                                        # the host rows are pageable: the copies must not outlive them
 
     def restart_replay(self, obs):
-        """After a jump (load_state, fork) the ring describes a past the envs no longer have: forget it and start from the current rows."""
+        """After a jump (load_state, fork) the ring describes a past the envs no longer have: forget it and start from the current rows;
+        so does the rollout."""
         if self.replay is not None:
             self.replay.clear()
-            self.commit_host_rows(obs)
+        self.commit_host_rows(obs)
+
+    # ------------------------------------------------------------------ the rollout the loop feeds
+    def attach_rollout(self, rollout):
+        self.rollout = rollout
+        self._buf = None                                                # the buffers gain the rollout's rows
+
+    def begin_rollout(self, obs):
+        """The rollout starts (again) from host rows - commit_host_rows calls this: the observation reset() returned, or the current one
+        after a jump (load_state, fork); steps gathered before it describe a past the envs no longer have."""
+        if self.rollout is None:
+            return
+        stream, d = self._buffers()
+        rows = d["robs"] if self.openai else d["obs"]
+        with torch.cuda.stream(stream):
+            rows.copy_(torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32).reshape(self.n, self.obs_dim)))
+            self.rollout.begin(rows)
+            stream.synchronize()                                        # the host rows are pageable: the copy must not outlive them

@@ -118,7 +118,7 @@ class VecHSREnv:
         self._loop = None              # device_loop.DeviceLoop: the torch side of auto_reset=True, which alone has one
         if self.auto_reset:
             from .device_loop import DeviceLoop
-            self._loop = DeviceLoop(sim, self.n_envs, model.nu, model.nq + model.nv, self.obs_dim)
+            self._loop = DeviceLoop(sim, self.n_envs, model.nu, model.nq + model.nv, self.obs_dim, openai=obs_type == "openai")
         self._goal_points = np.zeros((self.n_envs, 3), dtype=np.float32)
         self._plan = ResetPlan.from_env(model, self.starts, goals, block_space)      # what a reset samples and a step tests, parsed once
         self._parse_goals()
@@ -286,8 +286,28 @@ class VecHSREnv:
                                  seed=self._seed if seed is None else seed, env_offset=self.env_offset)
         self._loop.attach_replay(replay)
         self._get_observation()
-        self._loop.commit_host_rows(self._last_obs)
+        self._loop.commit_host_rows(self._last_obs)                     # (a rollout begins again too: the loop's tensors were made anew)
         return replay
+
+    # ------------------------------------------------------------------ on-policy rollouts on the device (rollout.py)
+    def make_rollout(self, horizon: int, gamma: float = 0.99, lam: float = 0.95, seed: Optional[int] = None):
+        """Attach a rollout.OnPolicyRollout of `horizon` env-steps to the device loop and return it: ``rollout.obs`` is what the policy acts
+        on, ``rollout.stage(action, logp, value)`` must precede every step(), which then closes the step with its reward, its reset kind and
+        the rows it returns; ``rollout.terminal_obs`` holds info['terminal_observation'] on the device for the critic's
+        ``rollout.bootstrap(...)``.  After `horizon` steps: ``finish``, ``minibatches``, ``next``.  reset(), load_state() and fork() start
+        the rollout again from the current rows.  Rows are this env's observations (25 floats with obs_type='openai').  seed None: the
+        env's seed; env_offset is passed on, so a shard draws its own shuffle."""
+        if self._loop is None:
+            raise ValueError("make_rollout needs auto_reset=True: the rollout is fed by the device loop, which only that mode runs")
+        if self._loop.rollout is not None:
+            raise ValueError("this env already feeds a rollout")
+        from .rollout import OnPolicyRollout
+        rollout = OnPolicyRollout(self.sim, horizon, obs_dim=self.obs_dim, gamma=gamma, lam=lam, seed=self._seed if seed is None else seed,
+                                  env_offset=self.env_offset)
+        self._loop.attach_rollout(rollout)
+        self._get_observation()
+        self._loop.begin_rollout(self._last_obs)
+        return rollout
 
     # ------------------------------------------------------------------ exact snapshots (sim.Snapshot; DESIGN.md)
     def _no_jump_while_recording(self, what):
@@ -305,7 +325,7 @@ class VecHSREnv:
 
     def load_state(self, state: EnvState):
         """sim.set_state() in its exact form (hsr/env.py:175; hsr/mujoco_env.py:87-94): no forward pass, nothing recomputed.  A replay made by
-        make_replay() is cleared: a ring of past transitions cannot follow a jump."""
+        make_replay() is cleared: a ring of past transitions cannot follow a jump; a rollout made by make_rollout() starts again."""
         self._no_jump_while_recording("load_state")
         if state.began != (self.goals is not None):
             raise ValueError("load_state: the state was saved on the other side of the first reset()")
@@ -322,7 +342,7 @@ class VecHSREnv:
     def fork(self, src, dst):
         """Envs `dst` become copies of env(s) `src` (one id for all, or one per destination), on the device, and continue bit for bit as
         their sources do; with auto_reset=True their next episodes are drawn with their own env ids.  A replay made by make_replay() is
-        cleared: a ring of past transitions cannot follow a jump."""
+        cleared: a ring of past transitions cannot follow a jump; a rollout made by make_rollout() starts again."""
         self._no_jump_while_recording("fork")
         dst = np.atleast_1d(np.asarray(dst, dtype=np.int32))
         src = np.broadcast_to(np.asarray(src, dtype=np.int32), dst.shape).copy()

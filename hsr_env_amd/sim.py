@@ -126,6 +126,18 @@ PROTOTYPES = {
     "hsr_replay_record_dev": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "hsr_replay_state": (_int, [_vp, _i32p, _i32p, C.POINTER(C.c_uint32)]),
     "hsr_replay_sample_dev": (_int, [_vp, C.c_uint32, _int, _float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hsr_batch_rollout_create": (_int, [_vp, _vp, C.POINTER(_vp)]),
+    "hsr_rollout_destroy": (None, [_vp]),
+    "hsr_rollout_begin_dev": (_int, [_vp, _vp]),
+    "hsr_rollout_stage_dev": (_int, [_vp, _vp, _vp, _vp]),
+    "hsr_rollout_close_dev": (_int, [_vp, _vp, _vp, _vp]),
+    "hsr_rollout_bootstrap_dev": (_int, [_vp, _vp]),
+    "hsr_rollout_finish_dev": (_int, [_vp, _vp]),
+    "hsr_rollout_next": (_int, [_vp]),
+    "hsr_rollout_state": (_int, [_vp, _i32p, _i32p]),
+    "hsr_rollout_stats": (_int, [_vp, _fp_t, _fp_t, _fp_t]),
+    "hsr_rollout_minibatch_dev": (_int, [_vp, C.c_uint32, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hsr_rollout_planes_dev": (_int, [_vp, _vp, _vp]),
 }
 EXPORTS = list(PROTOTYPES)
 
@@ -261,6 +273,11 @@ class BatchSim:
     def replay(self, spec: "ReplaySpec") -> "Replay":
         """An episode-aware transition ring on the device with a relabelling sampler, bound to this batch."""
         return Replay(self, spec)
+
+    # -- on-policy rollouts (include/hsrsim.h: hsr_batch_rollout_create ..; the class Rollout below, rollout.OnPolicyRollout on top of it)
+    def rollout(self, spec: "RolloutSpec") -> "Rollout":
+        """A store of `horizon` env-steps on the device with GAE, advantage statistics and shuffled minibatches, bound to this batch."""
+        return Rollout(self, spec)
 
     def copy_envs(self, src, dst):
         """env dst[i] <- env src[i] on the device, every source read before any destination is written; the destinations then continue
@@ -673,3 +690,72 @@ class Replay:
         """Minibatch `draw` of `batch` samples into device arrays (any None); include/hsrsim.h states the function."""
         _check(self.sim._L, self.sim._L.hsr_replay_sample_dev(self._r, int(draw) & 0xffffffff, int(batch), float(her_ratio), d_obs, d_act, d_next_obs,
                                                               d_goal, d_achieved_next, d_reward, d_done, d_index))
+
+
+class RolloutSpec(C.Structure):
+    """include/hsrsim.h: hsr_rollout_spec."""
+    _fields_ = [("seed", C.c_uint64), ("env_offset", C.c_uint32), ("horizon", C.c_int32), ("obs_dim", C.c_int32), ("gamma", C.c_float),
+                ("lam", C.c_float)]
+
+
+ROLLOUT_EMPTY, ROLLOUT_READY, ROLLOUT_STAGED, ROLLOUT_DONE = range(4)
+
+
+class Rollout:
+    """The on-policy rollout store of a batch (include/hsrsim.h: hsr_rollout) as the library exposes it: device pointers in, asynchronous
+    on the batch stream.  Its storage is released by close() or by close() of its batch, whichever comes first."""
+
+    def __init__(self, sim: BatchSim, spec: RolloutSpec):
+        self.sim, self.spec = sim, spec
+        self._r = C.c_void_p()
+        _check(sim._L, sim._L.hsr_batch_rollout_create(sim._b, C.byref(spec), C.byref(self._r)))
+
+    def close(self):
+        if getattr(self, "_r", None):
+            self.sim._L.hsr_rollout_destroy(self._r); self._r = None
+
+    __del__ = close
+
+    def begin_dev(self, d_obs):
+        """d_obs float32 [N, obs_dim]: what the policy acts on first; from any state to READY(0)."""
+        _check(self.sim._L, self.sim._L.hsr_rollout_begin_dev(self._r, d_obs))
+
+    def stage_dev(self, d_act, d_logp, d_value):
+        """Slot t: the head observation, d_act float32 [N, nu], d_logp and d_value float32 [N]."""
+        _check(self.sim._L, self.sim._L.hsr_rollout_stage_dev(self._r, d_act, d_logp, d_value))
+
+    def close_dev(self, d_reward, d_kind, d_next_obs):
+        """Slot t: d_reward float32 [N], d_kind uint8 [N] (episode_end_dev's reset kind); d_next_obs [N, obs_dim] becomes the head."""
+        _check(self.sim._L, self.sim._L.hsr_rollout_close_dev(self._r, d_reward, d_kind, d_next_obs))
+
+    def bootstrap_dev(self, d_value_terminal):
+        """float32 [N]: the critic's value of the terminal observation of the step closed last (read where kind == 2)."""
+        _check(self.sim._L, self.sim._L.hsr_rollout_bootstrap_dev(self._r, d_value_terminal))
+
+    def finish_dev(self, d_last_value):
+        """float32 [N]: V(head) after the last step; runs GAE and the statistics."""
+        _check(self.sim._L, self.sim._L.hsr_rollout_finish_dev(self._r, d_last_value))
+
+    def next(self):
+        _check(self.sim._L, self.sim._L.hsr_rollout_next(self._r))
+
+    def state(self):
+        """(state, steps closed): the host books, no device work."""
+        s, t = C.c_int32(0), C.c_int32(0)
+        _check(self.sim._L, self.sim._L.hsr_rollout_state(self._r, C.byref(s), C.byref(t)))
+        return int(s.value), int(t.value)
+
+    def stats(self):
+        """(mean, std, rstd) of the advantages as the device keeps them (float32); synchronises."""
+        m, s, r = C.c_float(0), C.c_float(0), C.c_float(0)
+        _check(self.sim._L, self.sim._L.hsr_rollout_stats(self._r, C.byref(m), C.byref(s), C.byref(r)))
+        return np.float32(m.value), np.float32(s.value), np.float32(r.value)
+
+    def minibatch_dev(self, epoch, first, count, normalize, d_obs=None, d_act=None, d_logp=None, d_value=None, d_adv=None, d_ret=None, d_index=None):
+        """Rows first .. first + count - 1 of the shuffle of `epoch` into device arrays (any None); include/hsrsim.h states the function."""
+        _check(self.sim._L, self.sim._L.hsr_rollout_minibatch_dev(self._r, int(epoch) & 0xffffffff, int(first), int(count), int(bool(normalize)), d_obs, d_act,
+                                                                  d_logp, d_value, d_adv, d_ret, d_index))
+
+    def planes_dev(self, d_adv=None, d_ret=None):
+        """The advantage and return planes, float32 [T, N] each (either None)."""
+        _check(self.sim._L, self.sim._L.hsr_rollout_planes_dev(self._r, d_adv, d_ret))

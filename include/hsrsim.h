@@ -380,6 +380,70 @@ int  hsr_replay_sample_dev(hsr_replay *r, uint32_t draw, int batch, float her_ra
                            float *d_obs, float *d_act, float *d_next_obs, float *d_goal, float *d_achieved_next,
                            float *d_reward, uint8_t *d_done, int32_t *d_index /*[batch,4]*/);
 
+/* ---- on-policy rollouts on the device: a rollout store, GAE with the time-limit bootstrap, advantage statistics, shuffled minibatches ----
+ * Opt-in; the on-policy twin of the replay above (PPO / A2C on a batch of lock-stepped envs).  Ownership as for the replay: a rollout is
+ * bound to the batch that made it and launches on hsr_batch_stream(); its storage goes with hsr_rollout_destroy, or with hsr_batch_destroy
+ * of its batch, whichever is first: after the latter the handle is still the caller's to destroy, and every other use returns HSR_EINVAL.
+ * A batch that never creates one allocates nothing.  A rollout reads nothing of the batch but N, nu and the stream, and is NOT part of an
+ * env record: after hsr_batch_snapshot_load* / hsr_batch_copy_envs* start it again with hsr_rollout_begin_dev.
+ *
+ * Storage for T = horizon steps of N envs: rows [T][N] of obs | act (obs_dim + nu words, padded to a multiple of 4); planes [T][N], env
+ * fastest, of logp, value, reward, kind, v_term, adv, ret; a head row [N][obs_dim]: the observation the policy acts on next.
+ * Rows and scalars move as 32-bit patterns (NaN payloads and -0 survive).
+ * Protocol (host state machine EMPTY, READY(t), STAGED, DONE; a call out of order returns HSR_EINVAL, launches nothing and leaves books and
+ * storage as they were):
+ *   begin(d_obs [N,obs_dim])    any state -> READY(0); head = d_obs
+ *   stage(d_act [N,nu], d_logp [N], d_value [N])    READY(t < T) -> STAGED; slot t: obs = head, act, logp, value
+ *   close(d_reward [N], d_kind [N], d_next_obs [N,obs_dim])    STAGED -> READY(t + 1); slot t: reward, kind, v_term = 0; head = d_next_obs.
+ *     d_kind is what hsr_batch_episode_end_dev writes: 0 the episode goes on; 2 it was cut by the time limit: GAE bootstraps from v_term;
+ *     any other value: terminal, no bootstrap.
+ *   bootstrap(d_value_terminal [N])    READY(t >= 1), state unchanged: v_term of slot t - 1 = d_value_terminal (the critic's value of the
+ *     terminal observation; read only where kind == 2); the last call wins.  A truncated step whose bootstrap was never called bootstraps
+ *     from 0.
+ *   finish(d_last_value [N] = V(head))    READY(T) -> DONE: GAE and the statistics below
+ *   next    DONE -> READY(0); the head row stays
+ *   minibatch, stats, planes    only in DONE
+ * GAE, per env, t = T-1 .. 0, every operation one float32 operation rounded on its own (no fma); gl = (float)gamma * (float)lam in float32:
+ *   nv    = kind[t] == 0 ? (t == T-1 ? last_value : value[t+1]) : kind[t] == 2 ? v_term[t] : 0
+ *   delta = (reward[t] + gamma nv) - value[t]
+ *   carry = (kind[t] == 0 && t < T-1) ? adv[t+1] : 0
+ *   adv[t] = delta + gl carry;   ret[t] = adv[t] + value[t]
+ * Statistics over all M = T N advantages, in fp64 with a fixed reduction shape (the same inputs give the same bits):
+ *   mean = sum(adv) / M;  var = sum((adv - mean)^2) / M (a second pass);  std = sqrt(var);  rstd = 1 / (std + 1e-8)
+ * each kept as the float32 rounding of its fp64 value.
+ * Shuffle of epoch `epoch`: a stateless bijection of [0, M), a four-round Feistel network with cycle walking.  Round keys k[0..3] = the
+ * Philox4x32-10 block of key (seed & 0xffffffff, seed >> 32), counter (epoch, 0, 5, env_offset).  bits = bit length of M - 1,
+ * h = max(1, (bits + 1) / 2), mask = 2^h - 1.  perm(i): x = i; repeat { L = x >> h, R = x & mask; for k in k[0..3]: (L, R) = (R, L ^ F(R, k));
+ * x = L << h | R } until x < M.  F(v, k) in uint32: v ^= k; v *= 0x9E3779B1; v ^= v >> 15; v *= 0x85EBCA77; v ^= v >> 13; return v & mask.
+ * minibatch(epoch, first, count, normalize, outputs): row i < count is element p = perm(first + i), t = p / N, e = p % N, of the store:
+ *   d_obs [count,obs_dim], d_act [count,nu], d_logp, d_value, d_ret [count] as stored; d_adv = normalize ? (adv - mean32) rstd32 (two
+ *   float32 operations) : adv; d_index [count,2] = (t, e).  Every output may be NULL; nothing is written past row count - 1.
+ *   HSR_EINVAL: count < 1, first < 0, first + count > M. */
+typedef struct hsr_rollout hsr_rollout;
+typedef struct hsr_rollout_spec {
+    uint64_t seed;
+    uint32_t env_offset;      /* as in hsr_episode_spec: salts the shuffle of a shard */
+    int32_t  horizon;         /* T: env-steps per rollout */
+    int32_t  obs_dim;         /* floats per observation row the caller will hand over (nq+nv, or 25 for 'openai') */
+    float    gamma;
+    float    lam;
+} hsr_rollout_spec;
+/* HSR_EINVAL (nothing allocated): a NULL argument, horizon < 1, obs_dim < 1 or above 2^20, gamma or lam not finite or outside [0, 1],
+ * T N >= 2^31, storage beyond 2^40 bytes.  HSR_EDEVICE: no device memory; what was allocated is freed. */
+int  hsr_batch_rollout_create(hsr_batch *b, const hsr_rollout_spec *spec, hsr_rollout **out);
+void hsr_rollout_destroy(hsr_rollout *r);
+int  hsr_rollout_begin_dev(hsr_rollout *r, const float *d_obs);
+int  hsr_rollout_stage_dev(hsr_rollout *r, const float *d_act, const float *d_logp, const float *d_value);
+int  hsr_rollout_close_dev(hsr_rollout *r, const float *d_reward, const uint8_t *d_kind, const float *d_next_obs);
+int  hsr_rollout_bootstrap_dev(hsr_rollout *r, const float *d_value_terminal);
+int  hsr_rollout_finish_dev(hsr_rollout *r, const float *d_last_value);
+int  hsr_rollout_next(hsr_rollout *r);
+int  hsr_rollout_state(hsr_rollout *r, int32_t *state, int32_t *t); /* host books, no device work: 0 EMPTY, 1 READY, 2 STAGED, 3 DONE; steps closed */
+int  hsr_rollout_stats(hsr_rollout *r, float *mean, float *std, float *rstd); /* waits for the stream */
+int  hsr_rollout_minibatch_dev(hsr_rollout *r, uint32_t epoch, int first, int count, int normalize,
+                               float *d_obs, float *d_act, float *d_logp, float *d_value, float *d_adv, float *d_ret, int32_t *d_index /*[count,2]*/);
+int  hsr_rollout_planes_dev(hsr_rollout *r, float *d_adv, float *d_ret); /* [T,N] copies of the advantage and return planes */
+
 /* diagnostics (meaningful only in the -DHSR_PHASE_TIMING build, libhsrsim_timing.so; tools/phase_timing.py,
  * tools/block_times.py): per-phase cycle sums of the last launches, and per-workgroup
  * {start, end (s_memrealtime), HW_ID, XCC_ID, Newton trips, sphere-cull candidates, work items, rows} */
