@@ -144,6 +144,10 @@ int hsr_batch_render_frames_dev(hsr_batch *b, const float *cam, int track_body, 
 int hsr_batch_bad_state(hsr_batch *b, uint8_t *out /*[N]*/);
 
 /* ---- introspection used by the parity tests (stage-by-stage comparison with the oracle) ------ */
+/* HSR_F_XPOS / HSR_F_XMAT: the link poses of the last forward pass.  After hsr_batch_reset / _set_state / _forward that is the pass over the
+ * current state; after hsr_batch_step* it is the forward pass of every env's LAST substep, that is the poses of the state that substep
+ * STARTED from (mj_step runs mj_forward, then integrates: sim.data.xpos after sim.step() lags qpos by one substep in the same way),
+ * with the free-joint quaternions normalised; persistent kernel and per-substep chain alike. */
 enum hsr_field { HSR_F_XPOS = 0 /*[N,nlink,3]*/, HSR_F_XMAT /*[N,nlink,9]*/, HSR_F_M /*[N,nv,nv]*/,
                  HSR_F_QACC /*[N,nv]*/, HSR_F_QACC_SMOOTH /*[N,nv]*/, HSR_F_QFRC_SMOOTH /*[N,nv]*/,
                  HSR_F_QFRC_CONSTRAINT /*[N,nv]*/, HSR_F_NCON /*[N] (as float)*/, HSR_F_NEFC /*[N]*/,

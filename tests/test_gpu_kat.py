@@ -107,6 +107,81 @@ def test_stacked_blocks_static_equilibrium(models):
     sim.close()
 
 
+def test_free_fall_closed_form(models):
+    """Twin of tests/test_kat.py::test_free_fall_closed_form: a lifted block in free flight over 50 substeps of the persistent kernel against
+    the closed form of semi-implicit Euler, v_n = -g h n, z_n = z0 - g h^2 n (n + 1) / 2 (smooth_ref.free_fall).  What fp32 leaves of it, worst
+    case: every substep rounds v (|v| < 1: half an ulp is at most 2^-25) and z (1 <= z < 2: 2^-24) once, and the acceleration m g / m comes out
+    of a factorisation and two triangular solves within 4 ulp of 9.81, relative 4 x 2^-23: |dv| <= 50 x 2^-25 + 0.981 x 2^-21 = 2.0e-6 and
+    |dz| <= 50 x 2^-24 + 50 h x 2.0e-6 = 3.2e-6.  Nothing else moves: x, y and the attitude stay exactly where they were put."""
+    from smooth_ref import free_fall
+    m = models["cfg2"]
+    n, nsub, h, z0 = 5, 50, m.timestep, 1.5
+    a, d = m.free_joint_qadrs()[0], m.nv - 6
+    q = np.tile(m.qpos0, (n, 1)); q[:, a:a + 3] = [0.0, 0.0, z0]
+    sim = hs.BatchSim(m, n)
+    assert sim.kernel_flags() == 7
+    sim.set_debug(True)
+    sim.set_state(np.zeros(n), q, np.zeros((n, m.nv)))
+    obs = sim.step(np.zeros((n, m.nu), np.float32), nsub)[0].astype(np.float64)
+    assert not sim.get_field(hs.F_NCON).any() and not sim.get_field(hs.F_NEFC).any()
+    z, vz = free_fall(z0, 0.0, nsub, h, G)
+    dv, dz = np.abs(obs[:, m.nq + d + 2] - vz).max(), np.abs(obs[:, a + 2] - z).max()
+    print(f"free fall, {nsub} substeps: |dv| {dv:.2e} (bound 2.0e-6), |dz| {dz:.2e} (bound 3.2e-6)")
+    assert dv <= 50 * 2.0 ** -25 + 0.981 * 2.0 ** -21 and dz <= 50 * 2.0 ** -24 + 50 * h * 2.0e-6
+    assert not obs[:, [a, a + 1]].any() and np.array_equal(obs[:, a + 3:a + 7], np.tile([1.0, 0, 0, 0], (n, 1)))
+    assert not obs[:, [m.nq + d, m.nq + d + 1, m.nq + d + 3, m.nq + d + 4, m.nq + d + 5]].any()
+    sim.close()
+
+
+def test_free_spin_conserves_angular_momentum(models):
+    """Twin of tests/test_kat.py::test_free_spin_conserves_angular_momentum: a torque-free tumbling block (cfg2, w = (4, 1, -3) in the body
+    frame) keeps its world-frame angular momentum R I w over 500 substeps (five calls of 100) to the 2 % that the CPU test allows the first-order
+    integrator; a missing or mis-signed gyroscopic term w x I w changes it by tens of per cent (the block's principal inertias differ 1 : 3)."""
+    from smooth_ref import free_joints, world_angular_momentum
+    m = models["cfg2"]
+    n = 5
+    a, d, link = free_joints(m)[0]
+    q = np.tile(m.qpos0, (n, 1)); q[:, a:a + 3] = [0.0, 0.0, 50.0]
+    v = np.zeros((n, m.nv)); v[:, d + 3:d + 6] = [4.0, 1.0, -3.0]
+    sim = hs.BatchSim(m, n)
+    assert sim.kernel_flags() == 7
+    sim.set_debug(True)
+    sim.set_state(np.zeros(n), q, v)
+    L0 = world_angular_momentum(m, link, q[0, a + 3:a + 7], v[0, d + 3:d + 6])
+    for call in range(5):
+        obs = sim.step(np.zeros((n, m.nu), np.float32), 100)[0].astype(np.float64)
+        assert not sim.get_field(hs.F_NCON).any()
+    L = np.array([world_angular_momentum(m, link, obs[e, a + 3:a + 7], obs[e, m.nq + d + 3:m.nq + d + 6]) for e in range(n)])
+    print(f"free spin, 500 substeps: L0 {L0}, L {L[0]}, largest relative change {np.abs(L / L0 - 1).max():.2e}")
+    assert np.allclose(L, L0, rtol=2e-2)
+    assert np.abs(obs[:, m.nq + d + 3:m.nq + d + 6] - v[:, d + 3:d + 6]).max() > 0.5          # it did tumble: the body-frame velocity has moved
+    sim.close()
+
+
+def test_quaternion_stays_unit_over_a_long_spin(models):
+    """Twin of tests/test_kat.py::test_quaternion_unit_norm_and_determinism (its state: cfg3, the block at (0.02, 0.05, 0.6) spinning at
+    w = (3, -2, 5), a fresh random ctrl every 100 substeps): after each of the four calls of 100 substeps the block's quaternion is within
+    4 ulp of unit norm - the integrator normalises q * dq every substep, so the error never accumulates.  That block lands on the pan after
+    a hundred substeps; every second env starts 20 m up and spins freely to the end."""
+    m = models["cfg3"]
+    n = 6
+    a, d = m.free_joint_qadrs()[0], m.nv - 6
+    q = np.tile(m.qpos0, (n, 1)); q[:, a:a + 3] = [0.02, 0.05, 0.6]
+    q[1::2, a + 2] = 20.0
+    v = np.zeros((n, m.nv)); v[:, d + 3:d + 6] = [3.0, -2.0, 5.0]
+    rng = np.random.default_rng(0)
+    sim = hs.BatchSim(m, n)
+    sim.set_state(np.zeros(n), q, v)
+    for call in range(4):
+        ctrl = np.tile(rng.uniform(m.act_ctrlrange[:, 0], m.act_ctrlrange[:, 1]), (n, 1))
+        obs = sim.step(ctrl, 100)[0].astype(np.float64)
+        off = np.abs(np.linalg.norm(obs[:, a + 3:a + 7], axis=1) - 1).max()
+        print(f"long spin, {100 * (call + 1)} substeps: | |quat| - 1 | = {off / 2.0 ** -23:.2f} ulp")
+        assert off <= 4 * 2.0 ** -23
+    assert not sim.bad_state()[1]
+    sim.close()
+
+
 def test_hull_on_a_plane_rests_on_several_points(models):
     """GPU twin of tests/test_kat.py::test_hull_on_a_plane_rests_on_several_points: the head-pan hull on the floor plane through the C-ABI.
     meshrest4 (up to four points per plane <-> convex pair): at rest on its flat face - three or four contacts, |angular velocity| < 5e-3,
