@@ -129,3 +129,14 @@ extern "C" int hsr_replay_sample_dev(hsr_replay *r, uint32_t draw, int batch, fl
     HIPCHK(hipGetLastError());
     return HSR_OK;
 }
+extern "C" int hsr_replay_sample_seq_dev(hsr_replay *r, uint32_t draw, int batch, int seq_len, float her_ratio, float gamma, const hsr_replay_seq_out *out) {
+    const int rc = replay_live(r, "hsr_replay_sample_seq_dev");
+    if (rc) return rc;
+    const char *why = replay_sample_seq_error(&r->books, batch, seq_len, her_ratio, gamma, out != nullptr);
+    if (why) return fail(HSR_EINVAL, "hsr_replay_sample_seq_dev: %s", why);
+    HIPCHK(hipSetDevice(r->device));
+    hipLaunchKernelGGL(k_replay_sample_seq, grid1((size_t)batch * (size_t)seq_len, REPLAY_PER_BLOCK), dim3(REPLAY_BLOCK), 0, r->owner->stream, r->dev,
+                       replay_first_slot(&r->books), replay_count(&r->books), draw, batch, seq_len, her_ratio, gamma, *out);
+    HIPCHK(hipGetLastError());
+    return HSR_OK;
+}

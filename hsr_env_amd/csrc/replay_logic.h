@@ -1,7 +1,7 @@
 // The host books of a replay (include/hsrsim.h: hsr_replay): row layout, the EMPTY -> READY -> PENDING state machine, slot arithmetic and
-// the argument checks, in plain C++ without a HIP call or header, so that a stand-alone program can exercise them under a sanitizer
-// (tests/replay_logic_main.cpp).  host_replay.h asks these functions and launches only what they allow; replay.h indexes with the same
-// row layout.
+// the argument checks, and the n-step reduction of a sampled window, in plain C++ without a HIP call or header, so that a stand-alone
+// program can exercise them under a sanitizer (tests/replay_logic_main.cpp, tests/replay_seq_logic_main.cpp).  host_replay.h asks these
+// functions and launches only what they allow; replay.h indexes with the same row layout and runs the same reduction.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -73,4 +73,43 @@ static inline const char *replay_sample_error(const ReplayBooks *k, int batch, f
     if (!isfinite(her_ratio) || her_ratio < 0.f || her_ratio > 1.f) return "her_ratio outside [0, 1]";
     return nullptr;
 }
+// hsr_replay_sample_seq_dev: what hsr_replay_sample_dev refuses, and the window's own numbers.  seq_len <= T keeps every per-sample loop
+// finite; batch seq_len < 2^31 keeps the (sample, step) index of the kernel and of every per-step output row inside an int.
+static inline const char *replay_sample_seq_error(const ReplayBooks *k, int batch, int seq_len, float her_ratio, float gamma, bool has_out) {
+    const char *why = replay_sample_error(k, batch, her_ratio);
+    if (why) return why;
+    if (!has_out) return "null out";
+    if (seq_len < 1) return "seq_len < 1";
+    if (seq_len > k->T) return "seq_len above capacity_steps";
+    if (!isfinite(gamma) || gamma < 0.f || gamma > 1.f) return "gamma outside [0, 1]";
+    if ((uint64_t)batch * (uint64_t)seq_len >= ((uint64_t)1 << 31)) return "batch x seq_len reaches 2^31";
+    return nullptr;
+}
 static inline void replay_clear_done(ReplayBooks *k) { k->state = REPLAY_EMPTY; k->pushed = 0; }
+
+// The n-step reduction of a window (include/hsrsim.h: hsr_replay_sample_seq_dev), for the kernel and for a host program alike.
+// step_at(k) gives reward and done of step k and is called for k = 0, 1, .. in order, once each, and not past the first done step.
+// m = the smallest k + 1 with done_k != 0 over k < length, else length; ret = sum over k < m of gamma^k reward_k, summed in that order;
+// discount = gamma^m; done = done_{m-1}.  Every product and every sum is a float32 operation of its own.
+#ifdef __HIPCC__
+#define REPLAY_HD __host__ __device__
+#else
+#define REPLAY_HD
+#endif
+struct ReplayStep { float reward; uint32_t done; };
+struct ReplayNstep { int m; float ret, discount; uint32_t done; };
+template <class StepAt> REPLAY_HD static inline ReplayNstep replay_nstep(int length, float gamma, StepAt step_at) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    ReplayNstep r{0, 0.f, 1.f, 0u};
+    for (int k = 0; k < length; k++) {
+        const ReplayStep s = step_at(k);
+        const float term = r.discount * s.reward;
+        r.ret = r.ret + term;
+        r.discount = r.discount * gamma;
+        r.m = k + 1; r.done = s.done;
+        if (s.done != 0u) break;
+    }
+    return r;
+}

@@ -271,7 +271,8 @@ class VecHSREnv:
         """Attach a replay.HindsightReplay to the device loop and return it: from now on every step() records its transition (between the
         step and the episode end, so the achieved goal is the one of the step, not of the next episode's start) and commits the
         observation it returns, and reset() commits too; ``replay.sample(batch_size)`` then draws relabelled minibatches without a copy
-        to the host.  Rows are this env's observations (25 floats with obs_type='openai').  seed None: the env's seed."""
+        to the host, and ``replay.sample_sequences(batch_size, seq_len, gamma)`` windows of up to seq_len steps inside one episode with
+        their n-step targets.  Rows are this env's observations (25 floats with obs_type='openai').  seed None: the env's seed."""
         if self._loop is None:
             raise ValueError("make_replay needs auto_reset=True: the replay is fed by the device loop, which only that mode runs")
         if self._plan.point_goal is None:

@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 
 from .device_loop import batch_stream, zero_tensors
-from .sim import BatchSim, ReplaySpec
+from .sim import BatchSim, ReplaySeqOut, ReplaySpec
 
 
 class HindsightReplay:
@@ -22,7 +22,8 @@ class HindsightReplay:
 
     Per env-step: ``record(ctrl, next_obs, reward, done)`` after ``sim.step_dev`` and before ``sim.episode_end_dev`` / any reset (the goal
     body's position is read from the batch at that moment), then ``commit(obs, reset)`` with the observation the policy acts on next and
-    the envs that start a new episode with it.  ``sample(batch_size)`` may run whenever no record waits for its commit.
+    the envs that start a new episode with it.  ``sample(batch_size)`` and ``sample_sequences(batch_size, seq_len)`` may run whenever no
+    record waits for its commit.
     Arguments are torch tensors on the batch's device (float32, uint8 for done / reset; reward / done None: what the step latched)."""
 
     def __init__(self, sim: BatchSim, capacity_steps: int, goal_body: int, geofence: float, obs_dim: int = None, her_ratio: float = 0.8,
@@ -36,6 +37,7 @@ class HindsightReplay:
         self._replay = sim.replay(spec)
         self._device, self._stream = batch_stream(sim)
         self._buffers = {}             # batch size -> the output tensors, allocated once
+        self._seq_buffers = {}         # (batch size, seq_len) -> the output tensors of sample_sequences
         self._draw = 0
 
     def _ptr(self, t, shape, dtype):
@@ -71,6 +73,31 @@ class HindsightReplay:
         self._draw = (self._draw + 1) & 0xffffffff
         return out
 
+    def sample_sequences(self, batch_size: int, seq_len: int, gamma: float = 0.99) -> dict:
+        """The next minibatch as windows of up to `seq_len` steps, for recurrent policies and n-step targets: the sampled step and the
+        steps after it inside its episode (never past the episode's end or the ring's newest step), all under one goal - the desired one,
+        or the achieved goal of a later step of the episode for a relabelled sample.  With L = seq_len: obs [B, L, obs_dim], action
+        [B, L, nu], next_obs, achieved_next [B, L, 3], reward [B, L], done [B, L] (uint8), zero past ``length`` [B] (int32, 1..L); goal
+        [B, 3]; index [B, 4] as in sample(), for the first step.  ``nstep`` [B] = m, the steps up to and including the first done one
+        (else ``length``), ``nstep_return`` = sum of gamma^k reward_k over them, ``nstep_discount`` = gamma^m, ``nstep_obs`` [B, obs_dim]
+        = next_obs of step m-1, ``nstep_done`` [B] (uint8).  A window cut by the time limit, by L or by the ring's newest step has
+        nstep_done = 0: bootstrap from nstep_obs, target = nstep_return + nstep_discount (1 - nstep_done) V(nstep_obs, goal).
+        Tensors are written on the batch's stream and overwritten by the next call of the same (batch_size, seq_len); the draw counter is
+        the one sample() advances."""
+        b, n = int(batch_size), int(seq_len)
+        out = self._seq_buffers.get((b, n))
+        if out is None:
+            f32, u8, i32 = torch.float32, torch.uint8, torch.int32
+            out = self._seq_buffers[(b, n)] = zero_tensors(self._device, dict(
+                obs=((b, n, self.obs_dim), f32), action=((b, n, self.sim.nu), f32), next_obs=((b, n, self.obs_dim), f32),
+                achieved_next=((b, n, 3), f32), goal=((b, 3), f32), reward=((b, n), f32), done=((b, n), u8), length=((b,), i32), nstep=((b,), i32),
+                nstep_return=((b,), f32), nstep_discount=((b,), f32), nstep_obs=((b, self.obs_dim), f32), nstep_done=((b,), u8),
+                index=((b, 4), i32)))
+        ptr = {"act" if k == "action" else k: v.data_ptr() for k, v in out.items()}
+        self._replay.sample_seq_dev(self._draw, b, n, self.her_ratio, gamma, ReplaySeqOut(**ptr))
+        self._draw = (self._draw + 1) & 0xffffffff
+        return out
+
     @property
     def stream(self):
         """The batch's stream as a torch stream: where record / commit / sample run."""
@@ -86,7 +113,7 @@ class HindsightReplay:
 
     def close(self):
         self._replay.close()
-        self._buffers = {}
+        self._buffers, self._seq_buffers = {}, {}
 
     def __len__(self):
         return self._replay.state()[0] * self.sim.n

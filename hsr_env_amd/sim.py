@@ -126,6 +126,7 @@ PROTOTYPES = {
     "hsr_replay_record_dev": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "hsr_replay_state": (_int, [_vp, _i32p, _i32p, C.POINTER(C.c_uint32)]),
     "hsr_replay_sample_dev": (_int, [_vp, C.c_uint32, _int, _float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hsr_replay_sample_seq_dev": (_int, [_vp, C.c_uint32, _int, _int, _float, _float, _vp]),
     "hsr_batch_rollout_create": (_int, [_vp, _vp, C.POINTER(_vp)]),
     "hsr_rollout_destroy": (None, [_vp]),
     "hsr_rollout_begin_dev": (_int, [_vp, _vp]),
@@ -653,6 +654,12 @@ class ReplaySpec(C.Structure):
                 ("goal_body", C.c_int32), ("geofence", C.c_float)]
 
 
+class ReplaySeqOut(C.Structure):
+    """include/hsrsim.h: hsr_replay_seq_out - device addresses, each may be None."""
+    _fields_ = [(name, C.c_void_p) for name in ("obs", "act", "next_obs", "achieved_next", "goal", "reward", "done", "length", "nstep", "nstep_return",
+                                                "nstep_discount", "nstep_obs", "nstep_done", "index")]
+
+
 class Replay:
     """The transition ring of a batch (include/hsrsim.h: hsr_replay) as the library exposes it: device pointers in, asynchronous on the
     batch stream.  Its storage is released by close() or by close() of its batch, whichever comes first."""
@@ -690,6 +697,12 @@ class Replay:
         """Minibatch `draw` of `batch` samples into device arrays (any None); include/hsrsim.h states the function."""
         _check(self.sim._L, self.sim._L.hsr_replay_sample_dev(self._r, int(draw) & 0xffffffff, int(batch), float(her_ratio), d_obs, d_act, d_next_obs,
                                                               d_goal, d_achieved_next, d_reward, d_done, d_index))
+
+    def sample_seq_dev(self, draw, batch, seq_len, her_ratio, gamma, out: "ReplaySeqOut"):
+        """Windows of up to `seq_len` steps and their n-step targets for minibatch `draw` into the device arrays of `out` (any None);
+        include/hsrsim.h states the function."""
+        _check(self.sim._L, self.sim._L.hsr_replay_sample_seq_dev(self._r, int(draw) & 0xffffffff, int(batch), int(seq_len), float(her_ratio), float(gamma),
+                                                                  None if out is None else C.byref(out)))
 
 
 class RolloutSpec(C.Structure):

@@ -383,6 +383,46 @@ int  hsr_replay_state(hsr_replay *r, int32_t *count, int32_t *head_slot, uint32_
 int  hsr_replay_sample_dev(hsr_replay *r, uint32_t draw, int batch, float her_ratio,
                            float *d_obs, float *d_act, float *d_next_obs, float *d_goal, float *d_achieved_next,
                            float *d_reward, uint8_t *d_done, int32_t *d_index /*[batch,4]*/);
+/* Episode segments and n-step targets (the windows of ReplayBuffer.sample(batch_size, seq_len), rl_utils/replay_buffer.py:59-66, made
+ * aware of episodes): the steps after a sampled one, inside its episode, under the same relabelled goal.  L = seq_len.
+ *   Draw: sample i takes the Philox block of hsr_replay_sample_dev - stream 4, counter (i, draw, 4, env_offset); e, j, relabel and
+ *     j_goal = j + mulhi(word3, j_end - j + 1) are as there; j_end, the last age with the ep_id of age j, is found for every sample.
+ *   Window: length = min(L, j_end - j + 1); step k < length is age j + k.  A window never leaves its episode and never passes the
+ *     ring's newest step.
+ *   Goal: goal = relabel ? achieved_next[j_goal] : desired[j] - one goal for the whole window.
+ *   Copied rows: obs, act, next_obs, achieved_next of step k are the rows of (e, slot(j + k)) as stored, moved as 32-bit patterns.
+ *   Reward and done of step k: not relabelled: as stored.  Relabelled: reach = norm(achieved_next[j + k] - goal) < geofence, the
+ *     expression of hsr_replay_sample_dev; reward = float(reach), done = reach.
+ *   Padding: steps k >= length are written as zero words in every per-step output (obs, act, next_obs, achieved_next, reward, done).
+ *   n-step: m = the smallest k + 1 with done_k != 0 over k < length, else length.  acc = 0, g = 1; for k = 0 .. m-1: acc = acc + g reward_k,
+ *     then g = g gamma - every product and every sum a float32 operation of its own.  nstep = m, nstep_return = acc, nstep_discount = g
+ *     (gamma^m), nstep_obs = next_obs[j + m - 1], nstep_done = done_{m-1}.  A window cut by the time limit, by L or by the ring's newest
+ *     step ends with nstep_done = 0: record stores the terminal observation as next_obs, so the caller bootstraps from nstep_obs,
+ *     target = nstep_return + nstep_discount (1 - nstep_done) V(nstep_obs, goal).
+ *   index[i] = (e, slot(j), relabelled ? slot(j_goal) : -1, relabelled), as hsr_replay_sample_dev gives it for the window's first step.
+ *   L = 1: the window equals hsr_replay_sample_dev with the same draw, bit for bit; for rewards 0 / 1, nstep_return = reward and
+ *     nstep_discount = gamma.
+ * Every pointer of `out` may be NULL.  The call is asynchronous on the batch stream, never writes the ring or the batch and allocates
+ * nothing.  HSR_EINVAL (nothing launched, outputs untouched): everything hsr_replay_sample_dev refuses; out == NULL; seq_len < 1 or
+ * seq_len > capacity_steps; gamma not finite or outside [0, 1]; batch * seq_len >= 2^31. */
+typedef struct hsr_replay_seq_out {      /* device pointers, each may be NULL; L = seq_len */
+    float *obs;            /* [batch, L, obs_dim] */
+    float *act;            /* [batch, L, nu] */
+    float *next_obs;       /* [batch, L, obs_dim] */
+    float *achieved_next;  /* [batch, L, 3] */
+    float *goal;           /* [batch, 3]  one goal per window */
+    float *reward;         /* [batch, L] */
+    uint8_t *done;         /* [batch, L] */
+    int32_t *length;       /* [batch]  valid steps, 1..L */
+    int32_t *nstep;        /* [batch]  m, 1..length */
+    float *nstep_return;   /* [batch] */
+    float *nstep_discount; /* [batch]  gamma^m */
+    float *nstep_obs;      /* [batch, obs_dim]  next_obs of step m-1 */
+    uint8_t *nstep_done;   /* [batch]  done of step m-1 */
+    int32_t *index;        /* [batch, 4]  as hsr_replay_sample_dev, for the window's first step */
+} hsr_replay_seq_out;
+int  hsr_replay_sample_seq_dev(hsr_replay *r, uint32_t draw, int batch, int seq_len, float her_ratio, float gamma,
+                               const hsr_replay_seq_out *out);
 
 /* ---- on-policy rollouts on the device: a rollout store, GAE with the time-limit bootstrap, advantage statistics, shuffled minibatches ----
  * Opt-in; the on-policy twin of the replay above (PPO / A2C on a batch of lock-stepped envs).  Ownership as for the replay: a rollout is

@@ -1,7 +1,7 @@
 """Cost of the hindsight replay next to the env-step it follows, and its sampler next to the torch-ops way, in one process.
 
     python tools/replay_bench.py [--config cfg3] [--envs 8192] [--substeps 300] [--capacity 64] [--batch 32768] [--her 0.8]
-                                 [--reps 20] [--warmup 3] [--loop-steps 8] [--rounds 3]
+                                 [--reps 20] [--warmup 3] [--loop-steps 8] [--rounds 3] [--seq-len 8 --gamma 0.99]
 
 cfg3, 8192 envs, 300 substeps per env-step, a ring of 64 env-steps per env, minibatches of 32768, her_ratio 0.8; blocks and goals from the
 benchmark's boxes, episodes of at most 20 env-steps.  HIP events on the batch stream around the asynchronous entry points.  One JSON line:
@@ -10,8 +10,11 @@ benchmark's boxes, episodes of at most 20 env-steps.  HIP events on the batch st
   (b) sample - hsr_replay_sample_dev, and the bytes it moves (row read + outputs written) over its median;
   (c) torch_sample - the same minibatch the way a user would build it today: the same fields in an rl.DeviceReplayBuffer (flat ring of
       T x N items, episode ids kept by torch ops on the reset mask), episode ends and 'future' relabelling in torch ops;
-  (d) closed_loop - env-steps/s of control.run on VecHSREnv(auto_reset=True) with and without make_replay(), alternating --rounds times.
-Medians with min and max; (b) and (c) alternate.  Needs the GPU.
+  (d) closed_loop - env-steps/s of control.run on VecHSREnv(auto_reset=True) with and without make_replay(), alternating --rounds times;
+  (e) with --seq-len L > 0: seq_sample - hsr_replay_sample_seq_dev, windows of up to L steps and their n-step targets - next to
+      torch_seq_sample, the same windows and targets from the same flat ring with torch ops: gather by slot, mask by episode id, the
+      n-step sums by cumulative products.
+Medians with min and max; (b) and (c) alternate, and so do the two legs of (e).  Needs the GPU.
 """
 from __future__ import annotations
 
@@ -41,6 +44,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--loop-steps", type=int, default=8)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--seq-len", type=int, default=0, help="0: leave (e) out")
+    ap.add_argument("--gamma", type=float, default=0.99)
     a = ap.parse_args()
     import torch
     from bench import GEOFENCE
@@ -49,7 +54,7 @@ def main():
     from hsr_env_amd.env import GoalSpec
     from hsr_env_amd.episodes import EpisodeSpec
     from hsr_env_amd.rl import DeviceReplayBuffer
-    from hsr_env_amd.sim import BatchSim, ReplaySpec
+    from hsr_env_amd.sim import BatchSim, ReplaySeqOut, ReplaySpec
     from hsr_env_amd.spaces import Box
     if not torch.cuda.is_available():
         raise SystemExit("replay_bench needs the GPU: a time measured anywhere else says nothing")
@@ -127,7 +132,7 @@ def main():
     count = T if buf.full else buf.pos // n
     ages = torch.arange(count, device=dev)
 
-    def torch_sample():
+    def torch_indices():
         e = torch.randint(0, n, (B,), device=dev, generator=gen)
         j = torch.randint(0, count, (B,), device=dev, generator=gen)
         relabel = torch.rand(B, device=dev, generator=gen) < a.her
@@ -137,6 +142,10 @@ def main():
         run = (ids == own) & (ages[:, None] >= j[None, :])
         j_end = j + run.sum(0) - 1
         j_goal = torch.minimum(j + (torch.rand(B, device=dev, generator=gen) * (j_end - j + 1).float()).long(), j_end)
+        return e, j, relabel, j_end, j_goal
+
+    def torch_sample():
+        e, j, relabel, j_end, j_goal = torch_indices()
         flat, flat_goal = ((first + j) % T) * n + e, ((first + j_goal) % T) * n + e
         achieved = b_ach[flat]
         goal = torch.where(relabel[:, None], b_ach[flat_goal], b_des[flat])
@@ -167,6 +176,52 @@ def main():
         s_ms.append(timed(device_sample)); t_ms.append(timed(torch_sample))
     row_bytes = 4 * ((2 * od + nu + 10 + 3) // 4 * 4)
     moved = B * (row_bytes + 4 * (2 * od + nu + 3 + 3 + 1 + 4) + 1)
+
+    # ---- (e) windows and n-step targets: the device sampler next to the torch-ops construction, on the same ring
+    L, seq = a.seq_len, None
+    if L > 0:
+        i32 = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)
+        seq_t = dict(obs=f32(B, L, od), act=f32(B, L, nu), next_obs=f32(B, L, od), achieved_next=f32(B, L, 3), goal=f32(B, 3), reward=f32(B, L),
+                     done=u8(B, L), length=i32(B), nstep=i32(B), nstep_return=f32(B), nstep_discount=f32(B), nstep_obs=f32(B, od), nstep_done=u8(B),
+                     index=i32(B, 4))
+        torch.cuda.synchronize()
+        seq_out = ReplaySeqOut(**{k: v.data_ptr() for k, v in seq_t.items()})
+        steps = torch.arange(L, device=dev)
+        powers = torch.tensor(a.gamma, dtype=torch.float32, device=dev) ** steps            # gamma^k
+        ones = torch.ones((B, 1), dtype=torch.float32, device=dev)
+
+        def device_seq_sample():
+            rep.sample_seq_dev(draw[0], B, L, a.her, a.gamma, seq_out)
+            draw[0] += 1
+
+        def torch_seq_sample():
+            e, j, relabel, j_end, j_goal = torch_indices()
+            length = torch.clamp(j_end - j + 1, max=L)
+            valid = steps[None, :] < length[:, None]                                    # [B, L]
+            age = torch.where(valid, j[:, None] + steps[None, :], j[:, None])
+            flat = ((first + age) % T) * n + e[:, None]                                 # [B, L] slots of the window in the flat ring
+            flat_goal = ((first + j_goal) % T) * n + e
+            mask = valid[:, :, None]
+            obs_w, act_w, next_w, ach_w = (torch.where(mask, x[flat], 0.0) for x in (b_obs, b_act, b_next, b_ach))
+            goal = torch.where(relabel[:, None], b_ach[flat_goal], b_des[flat[:, 0]])
+            reach = (b_ach[flat] - goal[:, None, :]).norm(dim=2) < GEOFENCE
+            reward = torch.where(relabel[:, None], reach.float(), b_rew[flat]) * valid
+            done_w = torch.where(relabel[:, None], reach, b_done[flat] != 0) & valid
+            # step k counts while no earlier step of the window was done: a cumulative product of (1 - done), shifted by one
+            alive = torch.cumprod(torch.cat([ones, 1.0 - done_w[:, :-1].float()], dim=1), dim=1) * valid
+            m = alive.sum(1).long()
+            ret = (alive * powers[None, :] * reward).sum(1)
+            last = (m - 1)[:, None]
+            return (obs_w, act_w, next_w, ach_w, goal, reward, done_w, length, m, ret, powers[m - 1] * a.gamma, b_next[flat.gather(1, last)[:, 0]],
+                    done_w.gather(1, last)[:, 0])
+
+        for _ in range(a.warmup):
+            timed(device_seq_sample); timed(torch_seq_sample)
+        q_ms, tq_ms = [], []
+        for _ in range(a.reps):
+            q_ms.append(timed(device_seq_sample)); tq_ms.append(timed(torch_seq_sample))
+        seq = (q_ms, tq_ms)
+        del seq_t
     rep.close(); sim.close()
     del buf, b_obs, b_act, b_next, b_ach, b_des, b_rew, b_done, b_id
     torch.cuda.empty_cache()
@@ -202,6 +257,8 @@ def main():
     plain, with_r = out["closed_loop_env_steps_per_s"]["plain"], out["closed_loop_env_steps_per_s"]["with_replay"]
     out["closed_loop_cost"] = 1.0 - with_r["median"] / plain["median"]
     out["closed_loop_plain_spread"] = (plain["max"] - plain["min"]) / plain["median"]
+    if seq:
+        out.update({"seq_len": L, "gamma": a.gamma, "seq_sample_ms": stat(seq[0]), "torch_seq_sample_ms": stat(seq[1])})
     print(json.dumps(out))
 
 
