@@ -252,18 +252,29 @@ __device__ __forceinline__ v3 support_vertex(const Geom &G, int vid) {
     else { const float4 w = G.verts[vid]; loc = mk3(w.x, w.y, w.z); }
     return mulmv(G.mat, loc) + G.pos;
 }
-template <int W = 1> __device__ __forceinline__ v3 support(const Geom &G, v3 dir, int *vid = nullptr) {
+// TM: the types the geom can have, bit t = type t (GEOM_TYPES_ANY: any).  A kernel instance that knows which types its model's convex pairs hold
+// (cfg_consts.h: cv_types) compiles only those arms - an arm that is never taken still costs a lone wave its compare, its exec-mask pair and its branch
+// on every call; for a geom whose type is in the mask the result is the same.
+enum { GEOM_TYPES_ANY = 0xff };
+template <int TM, int T> __device__ __forceinline__ bool geom_type_is(int type) {
+    if constexpr (((TM >> T) & 1) == 0) return false;
+    else return type == T;
+}
+// the masks of a kernel instance's model type: any type for the run-time DevModel, cv_types for a constant instance (as SolimpGeneral in solve_g.h)
+template <class T, class = void> struct ConvexTypes { static constexpr int first = GEOM_TYPES_ANY, second = GEOM_TYPES_ANY; };
+template <class T> struct ConvexTypes<T, std::enable_if_t<!std::is_same<T, DevModel>::value>> { static constexpr int first = T::cv_types & 0xff, second = (T::cv_types >> 8) & 0xff; };
+template <int W = 1, int TM = GEOM_TYPES_ANY> __device__ __forceinline__ v3 support(const Geom &G, v3 dir, int *vid = nullptr) {
     const v3 dl = mulmtv(G.mat, dir);
     v3 loc;
     if (vid) *vid = VID_NONE;
-    if (G.type == GEOM_BOX) {
+    if (geom_type_is<TM, GEOM_BOX>(G.type)) {
         loc = mk3(dl.x > 0 ? G.size.x : -G.size.x, dl.y > 0 ? G.size.y : -G.size.y, dl.z > 0 ? G.size.z : -G.size.z);
         if (vid) *vid = (dl.x > 0 ? 1 : 0) | (dl.y > 0 ? 2 : 0) | (dl.z > 0 ? 4 : 0);
-    } else if (G.type == GEOM_CYLINDER) {
+    } else if (geom_type_is<TM, GEOM_CYLINDER>(G.type)) {
         const float r2 = dl.x * dl.x + dl.y * dl.y, ir = frsq(r2);
         if (r2 > HSR_MINVAL * HSR_MINVAL) { loc.x = dl.x * ir * G.size.x; loc.y = dl.y * ir * G.size.x; } else { loc.x = 0; loc.y = 0; }
         loc.z = dl.z > 0 ? G.size.y : -G.size.y;
-    } else if (G.type == GEOM_SPHERE) {
+    } else if (geom_type_is<TM, GEOM_SPHERE>(G.type)) {
         loc = normalized(dl) * G.size.x;
     } else {
         // mesh hull: exhaustive search, first maximum wins (same tie-break as a sequential scan).  Two independent
@@ -277,21 +288,26 @@ template <int W = 1> __device__ __forceinline__ v3 support(const Geom &G, v3 dir
         // global memory (kin2.h: geom_cached3), so these are generic (flat) loads - a global_load here measured no faster (round 4)
         const float *gverts = (const float *)G.verts;
         auto gvert = [&](int i) { return make_float4(gverts[4 * i], gverts[4 * i + 1], gverts[4 * i + 2], 0.f); };
+        // A slot past the end of the hull reads vertex 0 again AS vertex 0: its value equals the one lane 0 found first and its index is 0, so where
+        // a lane takes it (its own vertices all lie below vertex 0's value, none of them the maximum) it holds a second copy of lane 0's candidate and
+        // the merge below picks what it picked before - the compare needs no bound test of its own (a scalar AND per slot, with its wait states).
         for (int i0 = 0; i0 < G.nvert; i0 += 4 * W) {
             float4 q[4];
+            int ic[4];
 #pragma unroll
-            for (int u = 0; u < 4; u++) { const int i = i0 + u * W + sub; q[u] = gvert(i < G.nvert ? i : 0); }
+            for (int u = 0; u < 4; u++) { const int i = i0 + u * W + sub; ic[u] = i < G.nvert ? i : 0; q[u] = gvert(ic[u]); }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                const int i = i0 + u * W + sub;
                 const float t = q[u].x * dl.x + q[u].y * dl.y + q[u].z * dl.z;
-                if (i < G.nvert && t > b) { b = t; idx = i; }
+                if (t > b) { b = t; idx = ic[u]; }
             }
         }
-        sup_merge<W>(b, idx, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b), 0xB1, 0xf, 0xf, false)), __builtin_amdgcn_update_dpp(0, idx, 0xB1, 0xf, 0xf, false));
-        if constexpr (W >= 4) sup_merge<W>(b, idx, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b), 0x4E, 0xf, 0xf, false)), __builtin_amdgcn_update_dpp(0, idx, 0x4E, 0xf, 0xf, false));
-        if constexpr (W >= 8) sup_merge<W>(b, idx, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b), 0x141, 0xf, 0xf, false)), __builtin_amdgcn_update_dpp(0, idx, 0x141, 0xf, 0xf, false));
-        if constexpr (W >= 16) sup_merge<W>(b, idx, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b), 0x140, 0xf, 0xf, false)), __builtin_amdgcn_update_dpp(0, idx, 0x140, 0xf, 0xf, false));
+        // (bound_ctrl: these four patterns read a lane of the own row that always exists, so the `old` operand is never used - without
+        // bound_ctrl the compiler has to zero the destination first, a copy per DPP move)
+        sup_merge<W>(b, idx, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b), 0xB1, 0xf, 0xf, true)), __builtin_amdgcn_update_dpp(0, idx, 0xB1, 0xf, 0xf, true));
+        if constexpr (W >= 4) sup_merge<W>(b, idx, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b), 0x4E, 0xf, 0xf, true)), __builtin_amdgcn_update_dpp(0, idx, 0x4E, 0xf, 0xf, true));
+        if constexpr (W >= 8) sup_merge<W>(b, idx, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b), 0x141, 0xf, 0xf, true)), __builtin_amdgcn_update_dpp(0, idx, 0x141, 0xf, 0xf, true));
+        if constexpr (W >= 16) sup_merge<W>(b, idx, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, b), 0x140, 0xf, 0xf, true)), __builtin_amdgcn_update_dpp(0, idx, 0x140, 0xf, 0xf, true));
         const float4 w = gvert(G.nvert > 0 ? idx : 0);
         loc = mk3(w.x, w.y, w.z);
         if (vid) *vid = G.nvert > 0 ? idx : 0;
@@ -715,11 +731,11 @@ __device__ int g_dbg_nsup_lane;   // unused placeholder to keep the symbol table
 #else
 #define DBG_COUNT_SUPPORT(ctr) do {} while (0)
 #endif
-template <int W = 1> __device__ __forceinline__ Sup mpr_support(const Geom &G1, const Geom &G2, v3 dir) {
+template <int W = 1, int TM1 = GEOM_TYPES_ANY, int TM2 = GEOM_TYPES_ANY> __device__ __forceinline__ Sup mpr_support(const Geom &G1, const Geom &G2, v3 dir) {
     Sup s;
     int i1, i2;
-    s.v1 = support<W>(G1, dir, &i1);
-    s.v2 = support<W>(G2, -dir, &i2);
+    s.v1 = support<W, TM1>(G1, dir, &i1);
+    s.v2 = support<W, TM2>(G2, -dir, &i2);
     s.id = i1 | (i2 << VID_BITS);
     s.v = s.v1 - s.v2;
     return s;
@@ -784,7 +800,8 @@ __device__ __forceinline__ bool reach_tol(const Sup &p1, const Sup &p2, const Su
 // The same six material points, placed with the present poses, are a portal again whenever the origin ray still passes through their
 // triangle (checked; else the search starts from scratch): the refinement then confirms the face it ended on last time with one or
 // two support calls instead of rediscovering it with eight.
-template <int W = 1> __device__ __forceinline__ bool mpr_penetration(const Geom &G1, const Geom &G2, float tol, int maxit, float &depth, v3 &dirout, v3 &pos, v3 &sep, int &nsup, int *warm = nullptr) {
+// TM1, TM2: the types G1 and G2 can have (support())
+template <int W = 1, int TM1 = GEOM_TYPES_ANY, int TM2 = GEOM_TYPES_ANY> __device__ __forceinline__ bool mpr_penetration(const Geom &G1, const Geom &G2, float tol, int maxit, float &depth, v3 &dirout, v3 &pos, v3 &sep, int &nsup, int *warm = nullptr) {
     const float eps = HSR_EPS;
     Sup p0, p1, p2, p3, v4;
     p0.v1 = G1.pos; p0.v2 = G2.pos; p0.v = p0.v1 - p0.v2; p0.id = 0;
@@ -806,7 +823,7 @@ template <int W = 1> __device__ __forceinline__ bool mpr_penetration(const Geom 
     if (warm) { warm[0] = warm[1] = warm[2] = 0; }
   cold_start:
   if (!warm_ok) {
-    p1 = mpr_support<W>(G1, G2, dir); nsup++;
+    p1 = mpr_support<W, TM1, TM2>(G1, G2, dir); nsup++;
     if (dot(p1.v, dir) < eps) { sep = dir; return false; }
     dir = cross(p0.v, p1.v);
     if (dot(dir, dir) < eps * eps) {
@@ -816,7 +833,7 @@ template <int W = 1> __device__ __forceinline__ bool mpr_penetration(const Geom 
         return true;
     }
     dir = normalized(dir);
-    p2 = mpr_support<W>(G1, G2, dir); nsup++;
+    p2 = mpr_support<W, TM1, TM2>(G1, G2, dir); nsup++;
     if (dot(p2.v, dir) < eps) { sep = dir; return false; }
     dir = normalized(cross(p1.v - p0.v, p2.v - p0.v));
     {
@@ -826,7 +843,7 @@ template <int W = 1> __device__ __forceinline__ bool mpr_penetration(const Geom 
     }
     for (int it = 0;; it++) {
         if (it > 100) return false;
-        p3 = mpr_support<W>(G1, G2, dir); nsup++;
+        p3 = mpr_support<W, TM1, TM2>(G1, G2, dir); nsup++;
         if (dot(p3.v, dir) < eps) { sep = dir; return false; }
         const bool c1 = dot(cross(p1.v, p3.v), p0.v) < -eps;
         const bool c2 = !c1 && dot(cross(p3.v, p2.v), p0.v) < -eps;
@@ -839,14 +856,14 @@ template <int W = 1> __device__ __forceinline__ bool mpr_penetration(const Geom 
     for (int it = 0;; it++) {
         dir = portal_dir(p1, p2, p3);
         if (dot(dir, p1.v) >= -eps) break;
-        v4 = mpr_support<W>(G1, G2, dir); nsup++;
+        v4 = mpr_support<W, TM1, TM2>(G1, G2, dir); nsup++;
         if (dot(v4.v, dir) < -eps) { sep = dir; return false; }
         if (reach_tol(p1, p2, p3, v4, dir, tol) || it > maxit) return false;
         expand_portal(p0, p1, p2, p3, v4);
     }
     for (int it = 0;; it++) {
         dir = portal_dir(p1, p2, p3);
-        v4 = mpr_support<W>(G1, G2, dir); nsup++;
+        v4 = mpr_support<W, TM1, TM2>(G1, G2, dir); nsup++;
         if (reach_tol(p1, p2, p3, v4, dir, tol) || it > maxit) {
             v3 pdir;
             bool interior;

@@ -326,6 +326,11 @@ static int derive_tables(hsr_batch *b, const hsr_model *m) {
         size_t cnt; const double *si = m->f64(nm, &cnt);
         for (size_t i = 4; si && i < cnt; i += 5) { const double pw = si[i] < 1 ? 1 : si[i]; if (pw != 1 && pw != 2) d.solimp_general = 1; }
     }
+    d.cv_types = 0;
+    {
+        const int *g1 = m->i32("pair_geom1"), *g2 = m->i32("pair_geom2"), *fn = m->i32("pair_fn"), *gt = m->i32("geom_type");
+        for (int p = 0; p < d.npair; p++) if (fn[p] == FN_CONVEX) d.cv_types |= (1 << (gt[g1[p]] & 7)) | (256 << (gt[g2[p]] & 7));
+    }
     return HSR_OK;
 }
 // the state arrays, [rows][N], zeroed; the counters and the work queue of the persistent kernel

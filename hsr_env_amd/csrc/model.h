@@ -13,6 +13,7 @@ struct DevModel {
     float timestep, impratio, gravz, tolerance, ls_tolerance, mpr_tolerance, meaninertia;
     int iterations, ls_iterations, mpr_iterations, any_damping;
     int solimp_general;              // some solimp power is neither 1 nor 2 (mj_makeImpedance's powf arms are needed); 0 for every committed model
+    int cv_types;                    // geom types of the FN_CONVEX pairs: bit t = some first geom has type t, bit 8 + t = some second geom has (collide.h: support<W, TM>)
     const int *link_parent, *link_dofadr, *link_dofnum, *link_qposadr, *link_free;
     const float *link_pos, *link_mat, *link_mass, *link_com, *link_inertia;
     const int *link_dofmask, *link_depth;   // depth of a link in the kinematic tree (world = 0)

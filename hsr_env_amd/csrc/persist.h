@@ -533,6 +533,7 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
                 // previous substep if the pair penetrated then (margin row = -1: rows 0-2 hold its vertex ids).
                 {
                     constexpr int MW = 8;          // lanes per convex-pair sub-group (4: -3 %, 16: -1 %)
+                    constexpr int TM1 = ConvexTypes<MT>::first, TM2 = ConvexTypes<MT>::second;      // the geom types this model's convex pairs hold, per side
                     const bool cv = fn == FN_CONVEX;
                     float cdx = 0.f, cdy = 0.f, cdz = 0.f, cmg = 0.f;
                     int cfresh = 0;
@@ -587,7 +588,7 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
                             bool still = false;                   // pass 1 found no margin left
                             PHASE_M(27);
                             if (have) {
-                                const float gap = -dot(support<MW>(H1, d) - support<MW>(H2, -d), d);
+                                const float gap = -dot(support<MW, TM1>(H1, d) - support<MW, TM2>(H2, -d), d);
                                 still = gap > 1e-7f;
                                 mg = still ? 0.98f * gap : 0.f;
                             }
@@ -595,7 +596,7 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
                             if (!still) {
                                 float depth; v3 dir, pos, sep;
                                 int nsup = 0;
-                                const bool hit = mpr_penetration<MW>(H1, H2, m.mpr_tolerance, m.mpr_iterations, depth, dir, pos, sep, nsup, wid);
+                                const bool hit = mpr_penetration<MW, TM1, TM2>(H1, H2, m.mpr_tolerance, m.mpr_iterations, depth, dir, pos, sep, nsup, wid);
 #ifdef HSR_PHASE_TIMING
                                 if ((tid & (MW - 1)) == 0) { atomicAdd(&sDbg[0], nsup); atomicAdd(&sDbg[1], 1); atomicMax(&sDbg[2], nsup); }
 #endif

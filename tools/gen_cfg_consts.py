@@ -14,7 +14,7 @@ from hsr_env_amd.compiler import load_config  # noqa: E402
 
 CONFIGS = ["cfg1", "cfg2", "cfg3", "cfg4", "cupboard"]
 INTS = ["nq", "nv", "nu", "nlink", "nbody", "ngeom", "npair", "nslot", "nconmax", "njmax", "nM", "ndense", "npair_pad", "nstatic_geom", "nfb",
-        "maxdepth", "iterations", "ls_iterations", "mpr_iterations", "any_damping", "solimp_general"]
+        "maxdepth", "iterations", "ls_iterations", "mpr_iterations", "any_damping", "solimp_general", "cv_types"]
 FLOATS = ["timestep", "impratio", "gravz", "tolerance", "ls_tolerance", "mpr_tolerance", "meaninertia"]
 
 
@@ -45,10 +45,16 @@ def consts(m):
         k += 1
     if nfb * 28 * (64 // group) > 4 * 48:
         nfb = 0
+    # geom types of the convex pairs (host_create.h: cv_types): bit t = a first geom of type t, bit 8 + t = a second geom of type t
+    cv = [p for p in range(npair) if a["pair_fn"][p] == 3]
+    cv_types = 0
+    for p in cv:
+        cv_types |= (1 << (int(a["geom_type"][a["pair_geom1"][p]]) & 7)) | (256 << (int(a["geom_type"][a["pair_geom2"][p]]) & 7))
     ints = dict(nq=nq, nv=nv, nu=nu, nlink=nlink, nbody=nbody, ngeom=ngeom, npair=npair, nslot=nslot, nconmax=nconmax, njmax=njmax,
                 nM=nv * (nv + 1) // 2, ndense=ndense, npair_pad=max((npair + 7) & ~7, 8), nstatic_geom=nstat, nfb=nfb, maxdepth=max(dep),
                 iterations=int(op[4]), ls_iterations=int(op[5]), mpr_iterations=int(op[8]), any_damping=int((a["dof_damping"] > 0).any()),
-                solimp_general=int(any(float(max(p, 1.0)) not in (1.0, 2.0) for arr in (a["dof_solimp"], a["pair_solimp"]) for p in arr.reshape(-1, 5)[:, 4])))
+                solimp_general=int(any(float(max(p, 1.0)) not in (1.0, 2.0) for arr in (a["dof_solimp"], a["pair_solimp"]) for p in arr.reshape(-1, 5)[:, 4])),
+                cv_types=cv_types)
     floats = dict(timestep=op[0], impratio=op[1], gravz=op[2], tolerance=op[3], ls_tolerance=op[6], mpr_tolerance=op[7], meaninertia=op[9])
     return ints, floats
 

@@ -1,4 +1,4 @@
-"""Issue slots spent on plain register copies, for one kernel of an `-S` listing: python tools/isa_copies.py LISTING.s SYMBOL-SUBSTRING [--all]
+"""Issue slots spent on plain register copies, for one kernel of an `-S` listing: python tools/isa_copies.py LISTING.s SYMBOL-SUBSTRING [--all | --lines FILE:A-B[,FILE:A-B..]]
 LISTING.s and the kernel as for tools/isa_slots.py (whose kernel_body / newton_window this uses); compiled with -gline-tables-only added,
 the listing carries `.loc` lines, which change no instruction, and every run is printed with the source line it belongs to.
 
@@ -9,7 +9,11 @@ by `x += ...`), so the runs of RUN_MIN or more are listed with their position.
 
 Printed: instructions, plain copies and v_cndmask of the whole kernel and of the Newton window; copies in runs of RUN_MIN or more; the runs
 (index of the first copy, length, `in window`), each with the innermost source line of its first copy and - as tools/isa_map.py attributes
-instructions - the last line of persist.h / solve_body.inc seen before it; with --all also the runs outside the window's neighbourhood."""
+instructions - the last line of persist.h / solve_body.inc seen before it; with --all also the runs outside the window's neighbourhood.
+
+--lines collide.h:242-326,collide.h:711-886 (listing with `.loc` lines): instead of the above, one row per INNERMOST source line inside the given
+ranges - instructions, plain copies, v_cndmask, SALU, SALU that touches the exec mask, branches, wait states - a total per file, and the sum
+copies + wait states + exec-mask SALU (the slots without arithmetic that tests/test_isa_mpr.py bounds for the MPR functions)."""
 import os
 import re
 import sys
@@ -67,6 +71,69 @@ def kernel_locs(listing: str, symbol: str):
     return out
 
 
+def innermost(locs):
+    """(file, line) of the innermost source line per instruction; an instruction the compiler made up (line 0) belongs to the last line seen before it."""
+    out, cur = [], ("?", 0)
+    for (f, l), _ in locs:
+        if l > 0: cur = (f, l)
+        out.append(cur)
+    return out
+
+
+def parse_lines(spec: str):
+    """'collide.h:711-886,persist.h:534-619' -> [(file, first, last)]"""
+    out = []
+    for part in spec.split(","):
+        f, _, r = part.partition(":")
+        a, _, b = r.partition("-")
+        out.append((f, int(a), int(b or a)))
+    return out
+
+
+def is_exec_salu(i) -> bool:
+    """scalar instruction that reads or writes the exec mask (what a divergent branch or a select under a lane condition is made of)"""
+    return i.op.startswith("s_") and not i.op.startswith(("s_cbranch", "s_branch", "s_waitcnt", "s_nop")) and ("saveexec" in i.op or "exec" in i.text.split(None, 1)[-1])
+
+
+ACCOUNT = ("instr", "copies", "cndmask", "salu", "exec", "branches", "nop_ws")
+
+
+def account(i):
+    """this instruction's contribution to the columns of ACCOUNT (nop_ws: wait states, an `s_nop N` is N + 1)"""
+    salu = i.op.startswith("s_") and not i.op.startswith(("s_cbranch", "s_branch", "s_waitcnt", "s_nop"))
+    return (1, int(is_copy(i)), int(i.op.startswith("v_cndmask")), int(salu), int(is_exec_salu(i)), int(i.op.startswith(("s_cbranch", "s_branch"))),
+            isa_slots.slots(i) if i.op == "s_nop" else 0)
+
+
+def line_account(ins, locs, ranges):
+    """{(file, line): [columns of ACCOUNT]} over the instructions whose innermost source line lies in one of `ranges` [(file, first, last)]."""
+    rows = {}
+    for i, (f, l) in zip(ins, innermost(locs)):
+        if not any(f == rf and a <= l <= b for rf, a, b in ranges): continue
+        row = rows.setdefault((f, l), [0] * len(ACCOUNT))
+        for k, v in enumerate(account(i)): row[k] += v
+    return rows
+
+
+def no_work_slots(rows) -> int:
+    """plain copies + wait states + exec-mask SALU of a line_account: issue slots that do no arithmetic (tests/test_isa_mpr.py bounds them)"""
+    c, e, w = ACCOUNT.index("copies"), ACCOUNT.index("exec"), ACCOUNT.index("nop_ws")
+    return sum(r[c] + r[e] + r[w] for r in rows.values())
+
+
+def print_line_account(ins, locs, ranges):
+    rows = line_account(ins, locs, ranges)
+    print(f"{'innermost line':22s} " + " ".join(f"{c:>8s}" for c in ACCOUNT))
+    tot = {}
+    for (f, l), r in sorted(rows.items()):
+        print(f"{f + ':' + str(l):22s} " + " ".join(f"{v:8d}" for v in r))
+        t = tot.setdefault(f, [0] * len(ACCOUNT))
+        for k, v in enumerate(r): t[k] += v
+    for f, t in sorted(tot.items()):
+        print(f"{f + ' (ranges)':22s} " + " ".join(f"{v:8d}" for v in t))
+    print(f"copies + wait states + exec-mask SALU: {no_work_slots(rows)}")
+
+
 def main(argv):
     if len(argv) < 3:
         raise SystemExit(__doc__)
@@ -74,6 +141,12 @@ def main(argv):
     name, ins = isa_slots.kernel_body(listing, argv[2])
     locs = kernel_locs(listing, argv[2])
     assert locs is None or len(locs) == len(ins)
+    lines = [a for k, a in enumerate(argv) if k and (argv[k - 1] == "--lines" or a.startswith("--lines="))]
+    if lines:
+        assert locs is not None, "--lines needs a listing compiled with -gline-tables-only"
+        print(name)
+        print_line_account(ins, locs, parse_lines(lines[0].split("=", 1)[-1]))
+        return
     tail = 3500 if "cfg4" in name else 1500
     lo, hi = isa_slots.newton_window(ins, tail)
     print(name)
