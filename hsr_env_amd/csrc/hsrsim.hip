@@ -29,6 +29,7 @@
 #include "episode.h"
 #include "snapshot.h"
 #include "replay.h"
+#include "replay_prio.h"
 #include "rollout.h"
 #include "cfg_consts.h"
 
@@ -41,5 +42,5 @@
 #include "host_access.h"     // settings, state / field getters and setters, diagnostics
 #include "host_render.h"     // ray-caster front end and in-step frame capture
 #include "host_snapshot.h"   // env records on the device: save / load / env-to-env copy, the host image (kernel: snapshot.h)
-#include "host_replay.h"     // hindsight replay: the transition ring and its sampler (kernels: replay.h; books and checks: replay_logic.h)
+#include "host_replay.h"     // hindsight replay: the transition ring and its sampler (kernels: replay.h, replay_prio.h; books and checks: replay_logic.h, replay_prio_logic.h)
 #include "host_rollout.h"    // on-policy rollouts: store, GAE, statistics, shuffled minibatches (kernels: rollout.h; books and checks: rollout_logic.h)

@@ -123,14 +123,12 @@ __device__ __forceinline__ ReplayWord replay_step_words(const ReplayDev &R, cons
 // checks 16 ages per pass, one per lane, on the ep_id plane; then the group copies the row, 16 bytes per lane, and routes its words to the
 // caller's arrays.  e < N, age < count and slot < T hold for every 32-bit draw (mulhi(w, n) < n), and a group past `batch` leaves at once:
 // nothing is read or written outside the ring or the first `batch` rows of an output.  `first` = slot of age 0.
-__global__ void __launch_bounds__(REPLAY_BLOCK) k_replay_sample(ReplayDev R, int first, int count, uint32_t draw, int batch, float her_ratio,
-                                                                uint32_t *obs, uint32_t *act, uint32_t *next_obs, uint32_t *goal, uint32_t *achieved_next,
-                                                                uint32_t *reward, uint8_t *done, int32_t *index) {
-    const int i = blockIdx.x * REPLAY_PER_BLOCK + threadIdx.x / REPLAY_GROUP, lane = threadIdx.x % REPLAY_GROUP;
-    if (i >= batch) return;
+// The body is a function of the sample's draw, so that the prioritised sampler (replay_prio.h) runs the same code from its own draw.
+__device__ __forceinline__ void replay_sample_rows(const ReplayDev &R, int first, int count, const ReplayDraw &d, int i, int lane,
+                                                   uint32_t *obs, uint32_t *act, uint32_t *next_obs, uint32_t *goal, uint32_t *achieved_next,
+                                                   uint32_t *reward, uint8_t *done, int32_t *index) {
     const ReplayLayout &L = R.L;
     const int N = R.N;
-    const ReplayDraw d = replay_draw(R, i, draw, count, her_ratio);
     const int e = d.e, j = d.j;
     const bool relabel = d.relabel;
     const int sj = replay_slot_of(R, first, j);
@@ -161,6 +159,13 @@ __global__ void __launch_bounds__(REPLAY_BLOCK) k_replay_sample(ReplayDev R, int
     if (done) done[i] = (uint8_t)(s.done != 0u);
     if (index) { int32_t *x = index + (size_t)i * 4; x[0] = e; x[1] = sj; x[2] = sg; x[3] = relabel ? 1 : 0; }
 }
+__global__ void __launch_bounds__(REPLAY_BLOCK) k_replay_sample(ReplayDev R, int first, int count, uint32_t draw, int batch, float her_ratio,
+                                                                uint32_t *obs, uint32_t *act, uint32_t *next_obs, uint32_t *goal, uint32_t *achieved_next,
+                                                                uint32_t *reward, uint8_t *done, int32_t *index) {
+    const int i = blockIdx.x * REPLAY_PER_BLOCK + threadIdx.x / REPLAY_GROUP, lane = threadIdx.x % REPLAY_GROUP;
+    if (i >= batch) return;
+    replay_sample_rows(R, first, count, replay_draw(R, i, draw, count, her_ratio), i, lane, obs, act, next_obs, goal, achieved_next, reward, done, index);
+}
 
 // sample_seq: 16 lanes per (sample, step) - batch x seq_len rows in flight.  Every group of a sample redraws the sample's Philox block and
 // rescans j_end on the ep_id plane (4-byte reads, cheaper than a dependency between kernels), so it knows the window's length by itself:
@@ -170,15 +175,11 @@ __global__ void __launch_bounds__(REPLAY_BLOCK) k_replay_sample(ReplayDev R, int
 // the group, all 16 lanes alike, so that the loads of a pass are in flight together; then the group copies next_obs of step m - 1.
 // Bounds: ages j .. j + length - 1 <= j_end < count; (sample, step) < batch seq_len < 2^31 (replay_sample_seq_error); a group past that
 // leaves at once.  No LDS, no atomics, no scratch.
-__global__ void __launch_bounds__(REPLAY_BLOCK) k_replay_sample_seq(ReplayDev R, int first, int count, uint32_t draw, int batch, int seq_len, float her_ratio,
-                                                                    float gamma, hsr_replay_seq_out O) {
-    const uint32_t gi = blockIdx.x * (uint32_t)REPLAY_PER_BLOCK + threadIdx.x / REPLAY_GROUP;
-    const int lane = threadIdx.x % REPLAY_GROUP;
-    if (gi >= (uint32_t)batch * (uint32_t)seq_len) return;
-    const int i = (int)(gi / (uint32_t)seq_len), k = (int)(gi - (uint32_t)i * (uint32_t)seq_len);
+// The body, from the sample's draw on (as replay_sample_rows): gi = the (sample, step) of the group, i its sample, k its step.
+__device__ __forceinline__ void replay_sample_seq_rows(const ReplayDev &R, int first, int count, const ReplayDraw &d, uint32_t gi, int i, int k, int lane,
+                                                       int seq_len, float gamma, const hsr_replay_seq_out &O) {
     const ReplayLayout &L = R.L;
     const int N = R.N;
-    const ReplayDraw d = replay_draw(R, i, draw, count, her_ratio);
     const int e = d.e, j = d.j;
     const int j_end = replay_episode_end(R, first, count, e, j, lane);
     const int length = min(seq_len, j_end - j + 1);
@@ -243,4 +244,12 @@ __global__ void __launch_bounds__(REPLAY_BLOCK) k_replay_sample_seq(ReplayDev R,
     if (O.nstep_discount) O.nstep_discount[i] = n.discount;
     if (O.nstep_done) O.nstep_done[i] = (uint8_t)(n.done != 0u);
     if (O.index) { int32_t *x = O.index + (size_t)i * 4; x[0] = e; x[1] = sj; x[2] = sg; x[3] = d.relabel ? 1 : 0; }
+}
+__global__ void __launch_bounds__(REPLAY_BLOCK) k_replay_sample_seq(ReplayDev R, int first, int count, uint32_t draw, int batch, int seq_len, float her_ratio,
+                                                                    float gamma, hsr_replay_seq_out O) {
+    const uint32_t gi = blockIdx.x * (uint32_t)REPLAY_PER_BLOCK + threadIdx.x / REPLAY_GROUP;
+    const int lane = threadIdx.x % REPLAY_GROUP;
+    if (gi >= (uint32_t)batch * (uint32_t)seq_len) return;
+    const int i = (int)(gi / (uint32_t)seq_len), k = (int)(gi - (uint32_t)i * (uint32_t)seq_len);
+    replay_sample_seq_rows(R, first, count, replay_draw(R, i, draw, count, her_ratio), gi, i, k, lane, seq_len, gamma, O);
 }

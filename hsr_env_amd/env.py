@@ -267,12 +267,15 @@ class VecHSREnv:
         return self._loop.sample_action()
 
     # ------------------------------------------------------------------ hindsight replay on the device (replay.py)
-    def make_replay(self, capacity_steps: int, her_ratio: float = 0.8, seed: Optional[int] = None):
+    def make_replay(self, capacity_steps: int, her_ratio: float = 0.8, seed: Optional[int] = None, prioritized: bool = False, alpha: float = 0.6,
+                    eps: float = 1e-6, **priority_options):
         """Attach a replay.HindsightReplay to the device loop and return it: from now on every step() records its transition (between the
         step and the episode end, so the achieved goal is the one of the step, not of the next episode's start) and commits the
         observation it returns, and reset() commits too; ``replay.sample(batch_size)`` then draws relabelled minibatches without a copy
         to the host, and ``replay.sample_sequences(batch_size, seq_len, gamma)`` windows of up to seq_len steps inside one episode with
-        their n-step targets.  Rows are this env's observations (25 floats with obs_type='openai').  seed None: the env's seed."""
+        their n-step targets.  Rows are this env's observations (25 floats with obs_type='openai').  seed None: the env's seed.
+        prioritized=True: samples are drawn by priority (|td| + eps)^alpha and carry importance weights; feed the learner's TD errors back
+        with ``replay.update_priorities(batch, td_error)`` (priority_options: p_max, max_batch of replay.HindsightReplay)."""
         if self._loop is None:
             raise ValueError("make_replay needs auto_reset=True: the replay is fed by the device loop, which only that mode runs")
         if self._plan.point_goal is None:
@@ -284,7 +287,8 @@ class VecHSREnv:
             raise ValueError("this env already feeds a replay")
         from .replay import HindsightReplay
         replay = HindsightReplay(self.sim, capacity_steps, self._plan.goal_body, self._plan.geofence, obs_dim=self.obs_dim, her_ratio=her_ratio,
-                                 seed=self._seed if seed is None else seed, env_offset=self.env_offset)
+                                 seed=self._seed if seed is None else seed, env_offset=self.env_offset, prioritized=prioritized, alpha=alpha, eps=eps,
+                                 **priority_options)
         self._loop.attach_replay(replay)
         self._get_observation()
         self._loop.commit_host_rows(self._last_obs)                     # (a rollout begins again too: the loop's tensors were made anew)

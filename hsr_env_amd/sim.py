@@ -127,6 +127,12 @@ PROTOTYPES = {
     "hsr_replay_state": (_int, [_vp, _i32p, _i32p, C.POINTER(C.c_uint32)]),
     "hsr_replay_sample_dev": (_int, [_vp, C.c_uint32, _int, _float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hsr_replay_sample_seq_dev": (_int, [_vp, C.c_uint32, _int, _int, _float, _float, _vp]),
+    "hsr_replay_priority_enable": (_int, [_vp, _vp]),
+    "hsr_replay_priority_state": (_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_float)]),
+    "hsr_replay_priority_sample_dev": (_int, [_vp, C.c_uint32, _int, _float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hsr_replay_priority_sample_seq_dev": (_int, [_vp, C.c_uint32, _int, _int, _float, _float, _vp, _vp]),
+    "hsr_replay_priority_update_dev": (_int, [_vp, C.c_uint64, _int, _vp, _vp]),
+    "hsr_replay_priority_read_dev": (_int, [_vp, _vp]),
     "hsr_batch_rollout_create": (_int, [_vp, _vp, C.POINTER(_vp)]),
     "hsr_rollout_destroy": (None, [_vp]),
     "hsr_rollout_begin_dev": (_int, [_vp, _vp]),
@@ -654,6 +660,11 @@ class ReplaySpec(C.Structure):
                 ("goal_body", C.c_int32), ("geofence", C.c_float)]
 
 
+class PrioritySpec(C.Structure):
+    """include/hsrsim.h: hsr_priority_spec."""
+    _fields_ = [("p_init", C.c_float), ("p_min", C.c_float), ("p_max", C.c_float), ("max_batch", C.c_int32)]
+
+
 class ReplaySeqOut(C.Structure):
     """include/hsrsim.h: hsr_replay_seq_out - device addresses, each may be None."""
     _fields_ = [(name, C.c_void_p) for name in ("obs", "act", "next_obs", "achieved_next", "goal", "reward", "done", "length", "nstep", "nstep_return",
@@ -703,6 +714,35 @@ class Replay:
         include/hsrsim.h states the function."""
         _check(self.sim._L, self.sim._L.hsr_replay_sample_seq_dev(self._r, int(draw) & 0xffffffff, int(batch), int(seq_len), float(her_ratio), float(gamma),
                                                                   None if out is None else C.byref(out)))
+
+    # -- priorities (include/hsrsim.h: hsr_replay_priority_*)
+    def priority_enable(self, spec: "PrioritySpec"):
+        """Only on an empty replay: a sum tree over the ring's cells; new transitions enter with the largest priority stored so far."""
+        _check(self.sim._L, self.sim._L.hsr_replay_priority_enable(self._r, C.byref(spec)))
+
+    def priority_state(self):
+        """(pushed, total, p_new) after a synchronisation of the batch stream; pushed is the sampled_at token of a sample taken now."""
+        n, t, p = C.c_uint64(0), C.c_double(0), C.c_float(0)
+        _check(self.sim._L, self.sim._L.hsr_replay_priority_state(self._r, C.byref(n), C.byref(t), C.byref(p)))
+        return int(n.value), float(t.value), float(p.value)
+
+    def priority_sample_dev(self, draw, batch, her_ratio, d_obs=None, d_act=None, d_next_obs=None, d_goal=None, d_achieved_next=None, d_reward=None,
+                            d_done=None, d_index=None, d_prob=None):
+        _check(self.sim._L, self.sim._L.hsr_replay_priority_sample_dev(self._r, int(draw) & 0xffffffff, int(batch), float(her_ratio), d_obs, d_act,
+                                                                       d_next_obs, d_goal, d_achieved_next, d_reward, d_done, d_index, d_prob))
+
+    def priority_sample_seq_dev(self, draw, batch, seq_len, her_ratio, gamma, out: "ReplaySeqOut", d_prob=None):
+        _check(self.sim._L, self.sim._L.hsr_replay_priority_sample_seq_dev(self._r, int(draw) & 0xffffffff, int(batch), int(seq_len), float(her_ratio),
+                                                                           float(gamma), None if out is None else C.byref(out), d_prob))
+
+    def priority_update_dev(self, sampled_at, batch, d_index, d_priority):
+        """d_index int32 [batch, 4] as a sample wrote it (env and slot are read), d_priority float32 [batch]; rows of cells overwritten
+        since `sampled_at` are skipped."""
+        _check(self.sim._L, self.sim._L.hsr_replay_priority_update_dev(self._r, int(sampled_at), int(batch), d_index, d_priority))
+
+    def priority_read_dev(self, d_leaves):
+        """The leaves, float32 [T, N], into a device array."""
+        _check(self.sim._L, self.sim._L.hsr_replay_priority_read_dev(self._r, d_leaves))
 
 
 class RolloutSpec(C.Structure):

@@ -423,6 +423,51 @@ typedef struct hsr_replay_seq_out {      /* device pointers, each may be NULL; L
 } hsr_replay_seq_out;
 int  hsr_replay_sample_seq_dev(hsr_replay *r, uint32_t draw, int batch, int seq_len, float her_ratio, float gamma,
                                const hsr_replay_seq_out *out);
+/* Prioritised replay (Schaul et al., "Prioritized Experience Replay", ICLR 2016): an opt-in sum tree over the ring's cells, a stratified
+ * sampler that draws a cell with probability priority / total, and updates from the learner's TD errors.  A replay that never calls
+ * hsr_replay_priority_enable allocates nothing more and behaves as above, bit for bit; hsr_replay_sample_dev and
+ * hsr_replay_sample_seq_dev stay the uniform functions on a replay with priorities.
+ *   Cells and leaves: a cell is (slot, env); its leaf has index c = slot N + e (env fastest: one record touches one contiguous run of N
+ *     leaves) and holds a float32 priority; a cell without a stored transition has leaf 0.
+ *   Tree: logically a complete binary tree over 2^h >= T N leaves, absent leaves 0; every inner node is left + right as ONE float64
+ *     addition of its children (leaves widened exactly).  The shape is fixed, so every node - and total, the root - is a function of the
+ *     leaves alone; there are no floating-point atomics.  (Stored: every sixth level; the levels between are rebuilt where needed.)
+ *   Descent for a target u >= 0 (float64): at a node with children (l, r) go left if u < l or r == 0, else u = u - l and go right.  With
+ *     total > 0 the leaf reached has a positive priority for every u, u == total included.
+ *   Draw: sample i of draw `draw` takes the Philox block of stream 6 - key as above, counter (i, draw, 6, env_offset).
+ *     r = ((word0 >> 5) 2^26 + (word1 >> 6)) 2^-53; u = ((double)i + r) / (double)batch, then u = u total (stratified; each operation a
+ *     float64 operation of its own).  The leaf reached gives (e, slot); its age is j = (slot - first + T) mod T with first = slot(0).
+ *     From there on the sample is hsr_replay_sample_dev's: relabel from word2, j_goal from word3 and j_end, rows moved as 32-bit
+ *     patterns, the relabelled reward by the same goal test, d_index with the same meaning.  d_prob[i] = (float)((double)leaf / total).
+ *   New transitions: record sets the N leaves of the slot it writes to p_new and re-sums their ancestors.  p_new = p_init at first and
+ *     after clear, then the running maximum of p_init and every priority an update has stored.  clear zeroes the tree.
+ *   Update (sampled_at, batch, d_index [batch,4], d_priority [batch]): only index[:,0] = e and index[:,1] = slot are read.  The value
+ *     stored is d_priority clamped into [p_min, p_max], NaN as p_max.  When several rows name one cell the largest clamped value wins,
+ *     whatever the order of the rows.  Ancestors are re-summed from their children.  Skipped silently: a row with e or slot out of range,
+ *     a cell that holds no transition, a stale cell.  Staleness: W = pushed + (a record is pending); k_s = the largest k < W with k mod T
+ *     == slot; the cell is live for the token iff k_s exists and k_s < sampled_at.  sampled_at is the 64-bit `pushed` at the time of the
+ *     sample (hsr_replay_priority_state).
+ *   hsr_replay_priority_sample_seq_dev: priority and d_prob are those of the window's first step, everything else is
+ *     hsr_replay_sample_seq_dev; with L = 1 it equals hsr_replay_priority_sample_dev bit for bit.
+ * All calls but hsr_replay_priority_state are asynchronous on the batch stream; nothing is allocated after enable (max_batch sizes the
+ * per-sample scratch the replay owns).  HSR_EINVAL, nothing launched: priorities not enabled; the batch destroyed; for the samplers
+ * everything the uniform twin refuses (a pending record, count == 0, batch < 1, ..); batch > max_batch; update: count == 0, batch < 1, a
+ * NULL array, sampled_at > pushed; enable: not in the EMPTY state, enabled already, a non-finite value, not 0 < p_min <= p_init <= p_max,
+ * max_batch < 1, T N > 2^30. */
+typedef struct hsr_priority_spec {
+    float   p_init;        /* priority of a new transition until an update stores a larger one */
+    float   p_min, p_max;  /* stored priorities are clamped into [p_min, p_max]; p_min > 0 keeps every stored transition reachable */
+    int32_t max_batch;     /* largest batch of a prioritised sample or update */
+} hsr_priority_spec;
+int  hsr_replay_priority_enable(hsr_replay *r, const hsr_priority_spec *spec);
+int  hsr_replay_priority_state(hsr_replay *r, uint64_t *pushed, double *total, float *p_new);   /* synchronises the stream; each may be NULL */
+int  hsr_replay_priority_sample_dev(hsr_replay *r, uint32_t draw, int batch, float her_ratio,
+                                    float *d_obs, float *d_act, float *d_next_obs, float *d_goal, float *d_achieved_next,
+                                    float *d_reward, uint8_t *d_done, int32_t *d_index /*[batch,4]*/, float *d_prob /*[batch]*/);
+int  hsr_replay_priority_sample_seq_dev(hsr_replay *r, uint32_t draw, int batch, int seq_len, float her_ratio, float gamma,
+                                        const hsr_replay_seq_out *out, float *d_prob /*[batch]*/);
+int  hsr_replay_priority_update_dev(hsr_replay *r, uint64_t sampled_at, int batch, const int32_t *d_index /*[batch,4]*/, const float *d_priority /*[batch]*/);
+int  hsr_replay_priority_read_dev(hsr_replay *r, float *d_leaves /*[T,N]*/);                     /* the leaves, for tests and checkpoints */
 
 /* ---- on-policy rollouts on the device: a rollout store, GAE with the time-limit bootstrap, advantage statistics, shuffled minibatches ----
  * Opt-in; the on-policy twin of the replay above (PPO / A2C on a batch of lock-stepped envs).  Ownership as for the replay: a rollout is

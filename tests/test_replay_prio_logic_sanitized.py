@@ -1,0 +1,23 @@
+"""The priorities' host logic (hsr_env_amd/csrc/replay_prio_logic.h: the spec and argument checks, the level sizes, the clamp and the
+staleness rule) is plain C++ that the kernels and a host program both compile, so a stand-alone program (tests/replay_prio_logic_main.cpp)
+runs it under AddressSanitizer and UndefinedBehaviorSanitizer here, as tests/test_replay_seq_logic_sanitized.py does for the window
+sampler.  Any report fails the test."""
+import shutil
+import subprocess
+from pathlib import Path
+
+import pytest
+
+HERE = Path(__file__).resolve().parent
+
+
+@pytest.mark.skipif(not shutil.which("g++"), reason="g++ not available")
+def test_replay_prio_logic_under_asan_ubsan(tmp_path):
+    exe = tmp_path / "replay_prio_logic"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-o", str(exe), str(HERE / "replay_prio_logic_main.cpp")])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120,
+                       env={"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
+    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
+    assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
+    assert r.stdout.startswith("ok ")
