@@ -63,10 +63,22 @@ extern "C" int hsr_batch_set_solo(hsr_batch *b, int servers, float trips) {
     if (trips > 0.f) b->solo_trips = trips;
     return b->kernel_sv ? HSR_OK : 1;          // 1: accepted, but this model's kernel instance has no server path (the setting has no effect)
 }
+extern "C" int hsr_batch_set_split(hsr_batch *b, int on, int period, float trips, int min_left, int extra_helpers) {
+    ENTER(b);
+    if (period < 0 || period >= SPLIT_MAX_SUBSTEPS || trips > 1000.f || min_left < 0 || extra_helpers < 0 || extra_helpers > SPLIT_MAX_EXTRA)
+        return fail(HSR_EINVAL, "hsr_batch_set_split: period 0..2047, trips <= 1000, min_left >= 0, extra_helpers 0..4096");
+    b->split = on != 0;
+    if (period > 0) b->split_period = period;
+    if (trips >= 0.f) b->split_trips = trips;
+    if (min_left > 0) b->split_min_left = min_left;
+    b->split_extra = extra_helpers;
+    return b->kernel && b->split_inst ? HSR_OK : 1;      // 1: accepted, but this batch's kernel instance never splits (the setting has no effect)
+}
 extern "C" int hsr_batch_solo_handovers(hsr_batch *b, int *out) {
     ENTER_DEV(b);
     if (!out) return fail(HSR_EINVAL, "null argument");
     const int rc = read_drained(b, out, b->ds.sq_ctl + 1, 1);
+    if (!b->handovers_counted) *out = 0;          // (the word is reset only in front of launches that count)
     return rc ? rc : queue_error(b);
 }
 extern "C" int hsr_batch_set_queue(hsr_batch *b, int mode, int chunk) {

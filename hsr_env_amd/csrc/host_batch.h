@@ -65,6 +65,14 @@ struct hsr_batch {
     bool queue_chunk_set = false;  // ... chosen by the caller (environment / hsr_batch_set_queue): no automatic choice then
     int solo_servers = 0;          // workgroups of a queued launch that run hard envs alone (persist.h; hsr_batch_set_solo / HSR_SOLO); 0 = off
     float solo_trips = 3.5f;       // hand-over threshold: Newton iterations per substep over a round
+    // hard envs handed over inside a launch without the queue (persist.h, split_logic.h; hsr_batch_set_split / HSR_SPLIT*)
+    bool handovers_counted = false;     // the last persistent launch counted hand-overs in sq_ctl (queued or splitting); else hsr_batch_solo_handovers says 0
+    bool split_inst = false;       // the kernel instance is one whose launches may split (host_create.h: kPersistInstances)
+    bool split = true;             // on by default: measured on the headline; HSR_SPLIT=0 / hsr_batch_set_split(b, 0, ...) turn it off
+    int split_period = 8;          // substeps between two check points of a wave (swept: 8 / 16 / 32)
+    float split_trips = 2.5f;      // an env is hard at this many Newton iterations per substep over the window (swept: 2.5 / 3.5 / 4.5)
+    int split_min_left = 40;       // no hand-over with fewer substeps ahead
+    int split_extra = 0;           // tests: workgroups without a task that start as helpers
     bool kernel_log = false;       // hsr_batch_set_profiling(b, 2): an event pair around every launch of the persistent kernel, no synchronisation
     std::vector<std::pair<hipEvent_t, hipEvent_t>> klog;
     // ray caster (hsr_batch_render*): its own tables and buffers, built on first use; it never touches the simulation state
@@ -144,7 +152,6 @@ static int require_captured_step(const hsr_batch *b, const char *who) {
     if (b->cap_every <= 0 || b->cap_rows <= 0) return fail(HSR_EINVAL, "%s: no captured step (hsr_batch_set_capture, then a step)", who);
     return HSR_OK;
 }
-enum { QUEUE_ROUNDS = 64 };        // rounds the work queue of the persistent kernel has room for (DevState::q_head / q_wpos / q_items)
 static inline dim3 grid1(size_t n, int t = 256) { return dim3((unsigned)((n + t - 1) / t)); }
 // the work queue's watchdog (persist.h: q_claim) tripped in some launch since the last check: the flag is sticky on the device (no launch
 // clears it) and only this function resets it, after reading it - every synchronising entry point ends with it

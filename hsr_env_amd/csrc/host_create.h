@@ -13,6 +13,10 @@ static void read_switches(hsr_batch *b) {
     b->sw.debug = set("HSR_DEBUG");                                               // set: print the chosen instance's resources
     if (set("HSR_SOLO")) b->solo_servers = atoi(env("HSR_SOLO"));                 // solo servers of a queued launch (hsr_batch_set_solo)
     if (atof(env("HSR_SOLO_TRIPS")) > 0) b->solo_trips = (float)atof(env("HSR_SOLO_TRIPS"));     // their hand-over threshold
+    if (set("HSR_SPLIT")) b->split = atoi(env("HSR_SPLIT")) != 0;                 // hard envs handed over inside a launch (hsr_batch_set_split)
+    if (atoi(env("HSR_SPLIT_PERIOD")) > 0) b->split_period = atoi(env("HSR_SPLIT_PERIOD"));      // substeps between its check points ...
+    if (set("HSR_SPLIT_TRIPS") && atof(env("HSR_SPLIT_TRIPS")) >= 0) b->split_trips = (float)atof(env("HSR_SPLIT_TRIPS"));      // ... its threshold (0: every live env counts as hard) ...
+    if (atoi(env("HSR_SPLIT_MIN_LEFT")) > 0) b->split_min_left = atoi(env("HSR_SPLIT_MIN_LEFT"));      // ... and the substeps that must remain
     if (set("HSR_QUEUE")) b->queue = atoi(env("HSR_QUEUE")) != 0;                 // work queue forced on / off (hsr_batch_set_queue)
     if (atoi(env("HSR_QUEUE_CHUNK")) > 0) b->queue_chunk = atoi(env("HSR_QUEUE_CHUNK"));         // substeps per round of the work queue ...
     b->queue_chunk_set = atoi(env("HSR_QUEUE_CHUNK")) > 0;                        // ... and no automatic choice then
@@ -31,19 +35,23 @@ struct PersistInstance {
     int group, nv;                 // ... this many lanes per env and (nv >= 0) exactly this many dofs
     bool tg;                       // pair / geom tables in global memory (LDS budget: 8 workgroups per CU)
     persist_fn fn, sv;             // the instance and its twin with the solo-server path (persist.h SV), or NULL
+    bool split = false;            // its launches may hand hard envs over inside the launch (persist.h): the arm models, whose envs differ in hardness
 };
+// (persist.h SplitOf: the instances that carry the hand-over code - the rows with `split` below)
+template <> struct SplitOf<DevModel_cfg3> : std::true_type {};
+template <> struct SplitOf<DevModel_cupboard> : std::true_type {};
 static const PersistInstance kPersistInstances[] = {
 #ifdef HSR_DEV_CFG3
     // development builds (tools/build_variants.py): only the cfg3 instance is compiled - a sixth of the build time
-    {2, 16, -1, false, k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3>, k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3, true>},
+    {2, 16, -1, false, k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3>, k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3, true>, true},
 #else
     {0, 16, -1, false, k_env_step_mf<16, 2, true, 0, false, DevModel_cfg1>, nullptr},                  // two orthogonal slides
     {1, 16, -1, false, k_env_step_mf<16, 8, true, 0, false, DevModel_cfg2>, k_env_step_mf<16, 8, true, 0, false, DevModel_cfg2, true>},      // the slides + one block
-    {2, 16, -1, false, k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3>, k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3, true>},    // arm + block
+    {2, 16, -1, false, k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3>, k_env_step_mf<16, 13, true, 7, false, DevModel_cfg3, true>, true},    // arm + block
     {3, 32, -1, false, k_env_step_mf<32, 25, true, 7, false, DevModel_cfg4>, nullptr},                 // arm + three blocks
     {3, 32, -1, true, k_env_step_mf<32, 25, true, 7, true, DevModel_cfg4>, nullptr},                   // 124 constraint rows per env (compiler.py: eff_njmax)
-    {4, 16, -1, false, k_env_step_mf<16, 13, true, -1, false, DevModel_cupboard>, k_env_step_mf<16, 13, true, -1, false, DevModel_cupboard, true>},   // cupboard with its tables in LDS (HSR_TABLES_GLOBAL=0: 7 workgroups per CU)
-    {4, 16, -1, true, k_env_step_mf<16, 13, true, -1, true, DevModel_cupboard>, k_env_step_mf<16, 13, true, -1, true, DevModel_cupboard, true>},      // 274 candidate pairs
+    {4, 16, -1, false, k_env_step_mf<16, 13, true, -1, false, DevModel_cupboard>, k_env_step_mf<16, 13, true, -1, false, DevModel_cupboard, true>, true},   // cupboard with its tables in LDS (HSR_TABLES_GLOBAL=0: 7 workgroups per CU)
+    {4, 16, -1, true, k_env_step_mf<16, 13, true, -1, true, DevModel_cupboard>, k_env_step_mf<16, 13, true, -1, true, DevModel_cupboard, true>, true},      // 274 candidate pairs
     {-1, 16, 13, false, k_env_step_mf<16, 13, true>, nullptr},                                          // ndense at run time
     {-1, 16, -1, false, k_env_step_mf<16, 16, false>, nullptr},
     {-1, 32, -1, false, k_env_step_mf<32, 32, false>, nullptr},
@@ -199,6 +207,7 @@ static int plan_persist(hsr_batch *b, const hsr_model *m) {
     if (!fits_persist(b, m) || !inst) { d.nfb = 0; return HSR_OK; }   // no instance: development builds carry one only
     b->kernel = inst->fn;
     b->kernel_sv = inst->sv;
+    b->split_inst = inst->split;
     b->persist = true;
     for (persist_fn f : {b->kernel, b->kernel_sv})
         if (f && b->persist_lds_bytes > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void *)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->persist_lds_bytes));
@@ -357,7 +366,8 @@ static int alloc_state(hsr_batch *b) {
     if ((rc = dalloc(b, &s.phase_cyc, 32 + 40 * 8192))) return rc;
     if ((rc = dalloc(b, &s.capstat, 12))) return rc;
     if ((rc = dalloc(b, &s.trips, N))) return rc;
-    if ((rc = dalloc(b, &b->d_slot_env, N + 64))) return rc;
+    // (a splitting launch gives every workgroup a task row of its own behind the tasks' rows: persist.h)
+    if ((rc = dalloc(b, &b->d_slot_env, 2 * (N + 64) + 4 * (size_t)SPLIT_MAX_EXTRA))) return rc;
     // work queue of the persistent kernel: up to QUEUE_ROUNDS rounds of one ticket per task (a task = the envs of one workgroup)
     const size_t tasks = (N + 1) / 2;
     if ((rc = dalloc(b, &s.q_head, QUEUE_ROUNDS))) return rc;
@@ -366,8 +376,9 @@ static int alloc_state(hsr_batch *b) {
     if ((rc = dalloc(b, &s.q_err, 1))) return rc;
     s.sq_cap = (int)N + 4096;
     if ((rc = dalloc(b, &s.sq_items, (size_t)s.sq_cap))) return rc;
-    if ((rc = dalloc(b, &s.sq_ctl, 4))) return rc;
+    if ((rc = dalloc(b, &s.sq_ctl, SPLIT_CTL_WORDS))) return rc;
     s.solo_servers = 0; s.solo_trips_x4 = 14; s.solo_min_left = 40;
+    s.split_period = 0; s.split_trips_x4 = 14; s.split_min_left = 40;
     s.q_chunk = 0;
     s.slot_env = nullptr;
     return HSR_OK;

@@ -79,43 +79,7 @@ static int grow_capture(hsr_batch *b, int cap_rows) {
     return upload_capture_desc(b, b->cap_every, b->cap_n);
 }
 
-// How one env-step runs on the persistent kernel.  More tasks than the GPU holds workgroups at once: persistent workgroups + the work
-// queue (persist.h), else one task per workgroup.  Pure arithmetic on the batch's settings: no HIP call, no state.
-struct PersistLaunch {
-    int tasks, grid;               // tasks = the envs of one workgroup each; workgroups launched
-    int chunk, rounds;             // substeps per round of the work queue and its rounds; rounds == 0: no queue
-    int solo_servers, solo_trips_x4, solo_min_left;      // DevState fields of a launch with solo servers; solo_servers == 0: none
-};
-static PersistLaunch plan_launch(int N, int group, int slots, int n_substeps, int queue, int queue_chunk, bool queue_chunk_set,
-                                 int solo_servers, float solo_trips, bool has_sv, bool schedule) {
-    PersistLaunch p{};
-    const int epb = 64 / group, T = (N + epb - 1) / epb;
-    int chunk = queue_chunk;
-    // many tasks per resident workgroup (65536 envs: eight) balance themselves: longer rounds there, fewer hand-overs through the state arrays
-    // and fewer rebuilds of the item lists (measured at 65536 envs, cfg3: rounds of 20 / 50 / 100 / 300 substeps: 833 / 856 / 841 / 779 k env-steps/s)
-    if (!queue_chunk_set && slots > 0 && T >= 4 * slots) chunk = 50;
-    while ((n_substeps + chunk - 1) / chunk > QUEUE_ROUNDS) chunk *= 2;
-    // solo servers need the queue (a hard env leaves its task at the end of a round) and the env -> slot table
-    // (a hand-over ticket packs env | substep << 20 into one int that must stay non-negative: fewer than 2048 substeps, at most 2^20 envs - beyond
-    // that the launch simply runs without servers)
-    const bool solo = has_sv && solo_servers > 0 && solo_servers <= 4096 && schedule && slots > 0 && n_substeps >= 3 * chunk && n_substeps < 2048 && N <= (1 << 20)
-                      && (T + solo_servers <= slots || 4 * solo_servers <= slots);
-    const bool qon = slots > 0 && n_substeps >= 2 * chunk && (solo || queue == 1 || (queue < 0 && T > slots));
-    p.tasks = T;
-    p.grid = T;
-    p.chunk = chunk;
-    if (qon) {
-        p.rounds = (n_substeps + chunk - 1) / chunk;
-        p.grid = T < slots ? T : slots;
-        if (solo) {
-            p.solo_servers = solo_servers;
-            p.solo_trips_x4 = (int)(4.f * solo_trips + 0.5f);
-            p.solo_min_left = 2 * chunk;
-            p.grid = std::min(slots, T + solo_servers);
-        }
-    }
-    return p;
-}
+// (how one env-step runs on the persistent kernel is decided by plan_launch, launch_plan.h: pure arithmetic that a host program tests)
 
 // the whole env-step in one launch of the persistent kernel: it reads ctrl and writes obs / reward / done / nsteps itself
 static int launch_persistent(hsr_batch *b, const StepIO &io, int n_substeps, int goal_body, float geofence) {
@@ -128,14 +92,20 @@ static int launch_persistent(hsr_batch *b, const StepIO &io, int n_substeps, int
     if (b->schedule)
         hipLaunchKernelGGL(k_schedule, dim3((b->N + SCHED_CHUNK - 1) / SCHED_CHUNK), dim3(1024), 0, st, b->ds, 64 / b->group, b->d_slot_env);
     const PersistLaunch p = plan_launch(b->N, b->group, b->slots, n_substeps, b->queue, b->queue_chunk, b->queue_chunk_set,
-                                        b->solo_servers, b->solo_trips, b->kernel_sv != nullptr, b->schedule);
+                                        b->solo_servers, b->solo_trips, b->kernel_sv != nullptr, b->schedule,
+                                        SplitSettings{b->split, b->split_inst, b->split_period, b->split_trips, b->split_min_left, b->split_extra});
     DevState dsl = b->ds;
+    b->handovers_counted = p.rounds > 0 || p.split.on;
     dsl.slot_env = b->schedule ? b->d_slot_env : nullptr;
     dsl.solo_servers = p.solo_servers;
     if (p.solo_servers > 0) { dsl.solo_trips_x4 = p.solo_trips_x4; dsl.solo_min_left = p.solo_min_left; }
     if (p.rounds > 0) {
         dsl.q_chunk = p.chunk;
         hipLaunchKernelGGL(k_queue_init, grid1((size_t)p.rounds * p.tasks), dim3(256), 0, st, dsl, p.tasks, p.rounds);
+    }
+    if (p.split.on) {
+        dsl.split_period = p.split.period; dsl.split_trips_x4 = p.split.trips_x4; dsl.split_min_left = p.split.min_left;
+        hipLaunchKernelGGL(k_split_init, dim3(8), dim3(256), 0, st, dsl);
     }
     hipEvent_t k0 = nullptr, k1 = nullptr;
     if (b->kernel_log) { hipEventCreate(&k0); hipEventCreate(&k1); hipEventRecord(k0, st); }

@@ -34,6 +34,7 @@
 #include "cfg_consts.h"
 
 #include "host_model.h"      // error message, blob loader, hsr_model_*, hull planes: plain C++, no HIP
+#include "launch_plan.h"     // QUEUE_ROUNDS, plan_launch: the persistent launch plan, plain C++ (tests/split_logic_main.cpp)
 #include "host_batch.h"      // the hsr_batch record; error / entry-guard macros; allocation, upload and staging helpers
 #include "util_kernels.h"    // layout / IO / reset / observation / capture kernels, k_queue_init, k_schedule
 #include "host_create.h"     // environment switches, kernel-instance table, plan_persist, model upload, hsr_batch_create / destroy

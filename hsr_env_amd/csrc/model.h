@@ -92,6 +92,11 @@ struct DevState {
     // reserved, servers without an env, tasks that finished their last round }
     int solo_servers, solo_trips_x4, solo_min_left, sq_cap;      // sq_cap = entries of sq_items: every env can be handed over once, every server holds one more ticket
     int *sq_items, *sq_ctl;
+    // hand-over of hard envs inside a launch WITHOUT the queue (persist.h; split_logic.h decides): a wave checks every split_period substeps
+    // whether two or more of its envs ran split_trips_x4 / 4 Newton iterations per substep or more over that window and, with split_min_left
+    // substeps or more ahead, gives all but the hardest to workgroups that have finished.  split_period == 0: off.  It reuses sq_items / sq_ctl
+    // (eight control words: persist.h SPLIT_*), which are idle in such a launch
+    int split_period, split_trips_x4, split_min_left;
     unsigned long long *capstat;     // [4] cap statistics (include/hsrsim.h: hsr_batch_cap_counts)
     unsigned long long *phase_cyc;   // diagnostic build only (HSR_PHASE_TIMING): per-phase cycle sums
 };

@@ -22,6 +22,7 @@
 #include "kin2.h"
 #include "kin3.h"
 #include "solve_mf.h"
+#include "split_logic.h"
 
 template <int G> struct PersistLayout {
     int R, MS, oRows, oCnt, oB, envf, oPoly, oKin, oPair, oGeomC, oGeomS, oLinkTab, total;
@@ -99,6 +100,90 @@ __device__ __forceinline__ void q_push(const DevState &s, int T, int task, int r
     if (threadIdx.x == 0 && last && s.sq_ctl) __hip_atomic_fetch_add(&s.sq_ctl[3], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);      // the solo servers leave when every task is through
 }
 
+// ---- hand-over of hard envs inside a launch without the work queue (DevState::split_period > 0; plan_launch / split_logic.h decide).
+// A wave advances at the pace of its hardest env per substep, so two hard envs in one wave cost more than either alone; which envs are
+// hard shows only while the launch runs.  From the moment the first workgroups finish, their wave slots are idle: a workgroup that has
+// finished its own task becomes a HELPER, and a wave that finds two or more hard envs among its own at a check point (split_decide) keeps
+// the hardest and gives the others to helpers, one each.  A helper runs the env through the ordinary code path - lane group 0 of a task
+// row of its own in the env -> slot table, the other groups out of range - so the env's results are the same bit for bit whoever runs it.
+// sq_ctl (zeroed in front of the launch by k_split_init, which also empties sq_items):
+//   [SPLIT_CLAIMED]   tickets taken by helpers          [SPLIT_RESERVED]  tickets reserved by donors (= hand-overs of the launch)
+//   [SPLIT_CREDITS]   helpers waiting minus envs promised to them       [SPLIT_FINISHED] / [SPLIT_STARTED]  workgroups with a task of their own
+// Donor (split_acquire, then the end of run_task): one fetch_sub on the credits per env; a result <= 0 is undone and the env stays.  A
+// donor never waits.  With a credit in hand it ends its run at the check point, writes the state of all its envs, fences, reserves ticket
+// p = RESERVED++ and stores env | substep << 20 into sq_items[p] (release).
+// Helper (split_wait): adds one credit and polls.  CLAIMED < RESERVED: it takes ticket h = CLAIMED by compare-and-swap and waits for
+// sq_items[h] - its donor is past every decision and only has stores ahead of it.  It gives up waiting when FINISHED == STARTED (no
+// workgroup that could still donate is running): it withdraws its credit with a fetch_sub and leaves if the old value was positive -
+// else a donor holds that credit, the ticket is on its way, and the helper stays for it (the last look before leaving).
+// Why this cannot hang or lose an env:
+//   * credits never exceed the helpers that are polling, and every successful fetch_sub of a donor leaves one polling helper that can
+//     only leave through a failed withdrawal - so every reserved ticket is claimed.  (While q_err is clear: a helper that leaves on the error
+//     path keeps its credit, and a donor that read q_err == 0 just before may still take it - that env stops at its check point, in a launch
+//     that is reported as drained anyway);
+//   * a helper waits for nothing but (a) a donor that already holds a credit - a running workgroup with no wait ahead of it - or (b)
+//     the counters of workgroups that HAVE started; a workgroup that has not started yet (a shared or partly occupied GPU) is not counted,
+//     so a helper never holds the slot such a workgroup needs.  It may start after all helpers have left: it then finds no credit and donates nothing;
+//   * no worker ever blocks on a helper and helpers never donate, so no cycle of waits can form;
+//   * every spin is bounded as in q_claim and sets q_err on overrun (the launch drains, hsr_batch_sync reports it); a raised q_err makes
+//     donors keep their envs and helpers leave.
+enum { SPLIT_CLAIMED = 0, SPLIT_RESERVED = 1, SPLIT_CREDITS = 2, SPLIT_FINISHED = 3, SPLIT_STARTED = 4, SPLIT_CTL_WORDS = 8 };
+// donor: one credit per lane group of `want`, as far as helpers are free; returns the groups that got one (wave-uniform)
+__device__ __forceinline__ unsigned split_acquire(const DevState &s, unsigned want) {
+    unsigned got = 0;
+    if (threadIdx.x == 0 && __hip_atomic_load(s.q_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
+        for (int j = 0; j < SPLIT_MAX_GROUPS; j++) {
+            if (!((want >> j) & 1u)) continue;
+            if (__hip_atomic_fetch_sub(&s.sq_ctl[SPLIT_CREDITS], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0) got |= 1u << j;
+            else { __hip_atomic_fetch_add(&s.sq_ctl[SPLIT_CREDITS], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+        }
+    }
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)got);
+}
+// helper: the next ticket's item (env | substep << 20), or -1: leave.  The whole wave polls with uniform control flow: its lanes read the
+// control words in ONE load (a single request for the cache line), lane 0 does the updates.  A poll sleeps ~14 us, far longer than the solo
+// servers' - up to two thousand helpers poll the same line, and a co-resident hard wave must not lose issue slots or memory bandwidth to them.
+__device__ __forceinline__ int split_wait(const DevState &s, bool no_task) {
+    auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+    const int lane = threadIdx.x;
+    if (lane == 0) __hip_atomic_fetch_add(&s.sq_ctl[SPLIT_CREDITS], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int item = -1;
+    bool err = false;
+    for (int spins = 0;; spins++) {
+        if (spins > (1 << 18) || ((spins & 15) == 0 && uni(__hip_atomic_load(s.q_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0)) { err = true; break; }      // seconds: something is broken
+        const int ctl = __hip_atomic_load(&s.sq_ctl[lane & (SPLIT_CTL_WORDS - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int h = __builtin_amdgcn_readlane(ctl, SPLIT_CLAIMED);
+        if (h < __builtin_amdgcn_readlane(ctl, SPLIT_RESERVED)) {
+            int won = 0;
+            if (lane == 0) { int expect = h; won = __hip_atomic_compare_exchange_strong(&s.sq_ctl[SPLIT_CLAIMED], &expect, h + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 1 : 0; }
+            if (!uni(won)) { __builtin_amdgcn_s_sleep(8); continue; }       // another helper took it: look again at once
+            for (int w = 0; h < s.sq_cap; w++) {          // the donor reserved the ticket after its last decision: the item is a few stores away
+                item = uni(__hip_atomic_load(&s.sq_items[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                if (item >= 0) break;
+                __builtin_amdgcn_s_sleep(32);
+                if (w > (1 << 22) || uni(__hip_atomic_load(s.q_err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) { err = true; break; }
+            }
+            break;
+        }
+        // (equal: every workgroup that had started had finished its task.  A look that is out of date only makes the helper leave early,
+        // which the withdrawal below makes safe: a workgroup that starts or decides later finds one credit less)
+        // A workgroup WITHOUT a task of its own (a test setting, resident next to all the tasks' workgroups: split_plan) does not take 0 == 0 for
+        // "all finished": it stays until a worker has counted itself - a bounded wait like the others
+        if (__builtin_amdgcn_readlane(ctl, SPLIT_FINISHED) >= __builtin_amdgcn_readlane(ctl, SPLIT_STARTED) && !(no_task && __builtin_amdgcn_readlane(ctl, SPLIT_STARTED) == 0)) {
+            int gone = 0;
+            if (lane == 0) {
+                if (__hip_atomic_fetch_sub(&s.sq_ctl[SPLIT_CREDITS], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0) gone = 1;      // withdrawn: nobody counts on this helper
+                else __hip_atomic_fetch_add(&s.sq_ctl[SPLIT_CREDITS], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                  // a donor holds the credit: its ticket is on the way
+            }
+            if (uni(gone)) break;
+        }
+        for (int k = 0; k < 4; k++) __builtin_amdgcn_s_sleep(127);
+    }
+    if (err) { if (lane == 0) __hip_atomic_store(s.q_err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return -1; }
+    if (item >= 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    return item;
+}
+
 // NVT: compile-time bound on nv (nv <= NVT <= G); the matrix loops of the solver run to NVT instead of G
 // EXACT: nv == NVT, known at compile time (the `j < nv` guards of the unrolled matrix loops fold away)
 // NDT (EXACT only, else -1): ndense at compile time - the dofs from NDT on never couple to another dof in M (free bodies)
@@ -108,6 +193,9 @@ __device__ __forceinline__ void q_push(const DevState &s, int T, int task, int r
 // immediates, and no scalar load / SGPR is spent on any of them; hsr_batch_create checks the values against the loaded model
 // SV: the instance carries the solo-server path (hsr_batch_set_solo): a second copy of the substep loop with its own register allocation; the
 // default instances are compiled without it, a launch with servers picks the SV one
+// the configurations whose launches may hand hard envs over inside the launch: the arm models, whose envs differ in hardness (cfg1 / cfg2 never
+// donate; their instances carry none of the code)
+template <class MT> struct SplitOf : std::false_type {};      // (the configurations are named next to kPersistInstances, host_create.h)
 template <int G, int NVT, bool EXACT, int NDT = -1, bool TG = false, class MT = DevModel, bool SV = false>
 __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restrict__ mp, DevState s, int n_substeps, int goal_body, float geofence, int flags, StepIO io) {
     // the ~90 model fields stay in (constant-cached) memory and are read where they are used, instead of sitting in - and
@@ -123,6 +211,11 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
     const bool hook_jv_per_contact = flags & 2, hook_majorant = flags & 4;      // tests: force the J v per contact / the PSD-majorant Newton step
     const bool hook_dense_chol = flags & 128;         // tests: the dense factorisation of the Newton Hessian even where the sparse one applies
     constexpr bool EXACT_CT = EXACT && !std::is_same<MT, DevModel>::value;      // sizes AND structure (nfb, ndense) known at compile time
+    // the instances whose launches may split (hand-over of hard envs inside a launch, above): 16 lanes per env, a constant configuration of an arm model
+    // (SplitOf, in step with kPersistInstances of host_create.h), no server path.  A workgroup with a task of its own is counted as started by its first instructions: the helpers look at that count
+    constexpr bool SPLIT_INST = !SV && G == 16 && EXACT_CT && SplitOf<MT>::value;
+    const bool split_on = SPLIT_INST && s.split_period > 0 && s.q_chunk == 0 && s.slot_env != nullptr;
+    if (split_on && tid0 == 0 && (int)blockIdx.x < (N + EPB - 1) / EPB) __hip_atomic_fetch_add(&s.sq_ctl[SPLIT_STARTED], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const bool hook_no_item_list = flags & 64;        // tests: cull every substep (the behaviour before the item list was kept over substeps)
     const bool hook_ignore_stamps = flags & 16;      // tests: trust a separation margin whatever its stamp (the behaviour before the stamps existed)
     const bool mpr_warm = !(flags & 8);       // the portal of a penetrating convex pair is carried to its next substep (hsr_batch_set_mpr_warm)
@@ -238,15 +331,23 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
     PHASE_T0();
 
   constexpr bool HAS_SOLO = SV && EXACT && G == 16 && !std::is_same<MT, DevModel>::value;      // server instances of the reference configurations
-  // one run of substeps [sub0, sub1) of a task (the envs of one lane-group set) - or, SOLO, of the single env solo_env in lane group 0
+  // one run of substeps [sub0, sub1) of a task (the envs of one lane-group set) - or, SOLO, of the single env solo_env in lane group 0.
+  // It leaves the substep it stopped at in run_stop: sub1, or - a splitting launch whose wave gave envs away at a check point - the substep of
+  // that check point; the state of every env is in the state arrays either way, and the caller goes on from there with the envs it kept
+  // (the shared solver body holds a plain `return`, so the lambda returns nothing)
+  int run_stop = 0;
   auto run_task = [&](auto solo_c, const int sub0, const int sub1, const int solo_env) {
     constexpr bool SOLO = decltype(solo_c)::value;
     constexpr bool REP = SOLO;
     (void)solo_env;
-    const bool first_run = sub0 == 0, last_run = sub1 >= n_substeps;
+    const bool first_run = sub0 == 0;
+    int sub_stop = sub1;                                   // wave-uniform: where this run ends
+    unsigned give = 0;                                     // wave-uniform: lane groups whose env goes to a helper at sub_stop
+    int split_check = split_on ? sub0 + s.split_period : -1;      // wave-uniform: the next check point (the window of run_trips ends there)
+    (void)give; (void)split_check;
     const bool fresh = io.ctrl != nullptr && first_run;       // HSREnv.step begins here: ctrl[:] = action, a fresh done flag (hsr/env.py:116,124)
     cap_con = cap_row = cap_item = nsub_run = own_trips = 0; bad_acc = trips_acc = 0; nsteps_e = 0;
-    int run_trips = 0;                                     // Newton iterations of this lane's env over this run (hand-over to a solo server)
+    int run_trips = 0;                                     // Newton iterations of this lane's env over this run (hand-over to a solo server) / over the window of a splitting launch
     // Item list of the narrowphase, kept over several substeps (HSR_SKIN > 0): it is built from culls that ask "closer than HSR_SKIN"
     // instead of "touching", and holds until some geom of some env of the workgroup may have moved half of that since (upper bounds of
     // the moves, the ones the separation margins of the convex pairs use).  A pair that is not on the list was farther apart than the
@@ -258,7 +359,9 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
     float acc_move = 0.f;                                  // this lane's env: bound on the move of any of its geoms since the list was built
     // ---------------- load the env state; it lives in registers for the whole run of substeps
     {
-        PERSIST_LANE_VIEW(tid0)
+        int tid_r = tid0;
+        asm volatile("" : "+v"(tid_r));      // (a run's addresses are computed inside the task loop, not kept in - and spilled from - registers across it)
+        PERSIST_LANE_VIEW(tid_r)
         if (c == 0) { sEnv[g] = e; sTick[g] = s.tick[e]; }
         done = !in_range || (fresh ? false : s.done[e] != 0);
         qpos_c = 0; qvel_c = 0; warm_c = 0;
@@ -278,11 +381,32 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
         // a workgroup that carries a hard env (many Newton iterations per substep so far) sets the pace of the launch: it
         // gets issue priority over the wave it shares its SIMD with, which has slack
         if (sub - sub0 >= 4 && 2 * trips_acc > 5 * (sub - sub0)) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);      // A/B on the bench: +4 %
+        // ---------------- check point of a splitting launch: every split_period substeps the wave asks whether two or more of its envs were
+        // hard over the window; if so, and if helpers are free, it keeps the hardest and ends this run here (wave-uniform; lane 0 touches
+        // global memory only when the decision says "donate")
+        if constexpr (SPLIT_INST && !SOLO) {
+            if (sub == split_check) {
+                split_check += s.split_period;
+                int wt[EPB];
+#pragma unroll
+                for (int j = 0; j < EPB; j++) wt[j] = __builtin_amdgcn_readlane(run_trips, j * G);
+                run_trips = 0;
+                const unsigned long long ab = __ballot(!done && tid0 % G == 0);
+                unsigned alive = 0;
+#pragma unroll
+                for (int j = 0; j < EPB; j++) alive |= (unsigned)((ab >> (j * G)) & 1ull) << j;
+                const unsigned want = split_decide(wt, alive, EPB, sub, n_substeps - sub, s.split_period, s.split_trips_x4, s.split_min_left);
+                if (want) {
+                    give = split_acquire(s, want);
+                    if (give) sub_stop = sub;
+                }
+            }
+        }
         int tid_l = tid0;
         asm volatile("" : "+v"(tid_l));
         PERSIST_LANE_VIEW(tid_l)
         const bool valid = !done;
-        if (!wave_any(valid)) break;
+        if (!wave_any(valid) || give) break;
         if (valid && c == 0) sTick[g] += 1;      // read by the convex-pair section of ANY lane group, several wave_syncs further down
         int bad = 0;                 // per substep; only a live env's flag is kept
         asm volatile("" ::: "memory");   // model constants are re-read (L2 hits) every substep instead of living in - and spilling from - registers
@@ -718,9 +842,12 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
             PHASE(18);
         }
     }
+    const bool last_run = sub_stop >= n_substeps;
     // ---------------- write the state back (struct-of-arrays)
     {
-    PERSIST_LANE_VIEW(tid0)
+    int tid_w = tid0;
+    asm volatile("" : "+v"(tid_w));      // (as in the substep loop: nothing of the prologue's lane view is kept in registers for this one)
+    PERSIST_LANE_VIEW(tid_w)
     const int was_done = in_range ? s.done[e] : 0;
     if (in_range && (fresh || !(was_done != 0 && nsteps_e == 0))) {
         if (c < nq) s.qpos[(size_t)c * N + e] = qpos_c;
@@ -776,7 +903,26 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
             }
         }
     }
+    // Hand-over of a splitting launch: the envs of `give` leave this wave.  Their state is in the state arrays (written above) and out
+    // before the ticket is (release fence of every lane); the slot of the task is emptied, so that the caller's next run finds the
+    // group out of range; the ticket tells a helper the env and the substep to go on from.
+    if constexpr (SPLIT_INST && !SOLO) {
+        if (give) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            __builtin_amdgcn_wave_barrier();
+            if (c == 0 && ((give >> g) & 1u)) {
+                const int pos = __hip_atomic_fetch_add(&s.sq_ctl[SPLIT_RESERVED], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                s.slot_env[task * EPB + g] = -1;
+                ENV_STAMP(1, e, (unsigned long long)sub_stop | (__builtin_amdgcn_s_memrealtime() << 16));
+                if (pos < s.sq_cap) __hip_atomic_store(&s.sq_items[pos], e | (sub_stop << 20), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                else __hip_atomic_store(s.q_err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (cannot happen: an env is handed over at most once per launch)
+            }
+            __threadfence_block();       // the emptied slots are read by every lane of the group at the start of the next run
+            wave_sync();
+        }
     }
+    }
+    run_stop = sub_stop;
   };      // run_task
   if (HAS_SOLO && s.q_chunk && s.solo_servers > 0 && (int)blockIdx.x < s.solo_servers) {
     // ---------------- solo server: no tasks; one hard env at a time, alone in this wave, from the substep its worker left it at to the
@@ -812,15 +958,41 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
         if (threadIdx.x == 0) __hip_atomic_fetch_add(&s.sq_ctl[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // free again
       }
     }
-  } else
-  for (;;) {      // task loop (a single pass without the work queue)
+  } else {
+  // a splitting launch: the workgroups beyond the tasks' (a test setting) own no task and start as helpers; the others were counted as
+  // started at the top and are counted as finished after the last substep of their own task
+  const int n_tasks = (N + EPB - 1) / EPB;
+  bool helper = split_on && (int)blockIdx.x >= n_tasks;
+  int sub_next = 0;                  // where the next run of a splitting launch starts: 0, the check point the last run ended at, or a ticket's substep
+  for (;;) {      // task loop (a single pass without the work queue and the split)
     if (s.q_chunk) {
-        if (!q_claim(s, (N + EPB - 1) / EPB, (n_substeps + s.q_chunk - 1) / s.q_chunk, q_rlo, task, q_round)) break;
+        if (!q_claim(s, n_tasks, (n_substeps + s.q_chunk - 1) / s.q_chunk, q_rlo, task, q_round)) break;
+    } else if (helper) {
+        // one env of a wave that had two hard ones, alone in lane group 0 of this workgroup's own row of the env -> slot table
+        const int item = split_wait(s, (int)blockIdx.x >= n_tasks);
+        if (item < 0) break;
+        task = n_tasks + (int)blockIdx.x;
+        int tid_h = tid0;
+        asm volatile("" : "+v"(tid_h));      // (the row's address is computed here, not kept in a register pair for the whole launch)
+        if (tid_h < EPB) s.slot_env[task * EPB + tid_h] = tid_h == 0 ? (item & 0xfffff) : -1;
+        __threadfence_block();
+        wave_sync();
+        sub_next = item >> 20;
     }
-    const int sub0 = s.q_chunk ? q_round * s.q_chunk : 0, sub1 = s.q_chunk ? min(n_substeps, sub0 + s.q_chunk) : n_substeps;
+    const int sub0 = s.q_chunk ? q_round * s.q_chunk : sub_next, sub1 = s.q_chunk ? min(n_substeps, sub0 + s.q_chunk) : n_substeps;
     run_task(std::false_type{}, sub0, sub1, -1);
-    if (!s.q_chunk) break;
-    q_push(s, (N + EPB - 1) / EPB, task, q_round, sub1 >= n_substeps);
+    sub_next = run_stop;
+    if (s.q_chunk) { q_push(s, n_tasks, task, q_round, sub1 >= n_substeps); continue; }
+    if (!split_on) break;
+    if (sub_next < n_substeps) continue;       // the wave gave envs away: it goes on from the check point with the ones it kept
+    // the task is through (this workgroup's own, or a ticket's env): from now on the workgroup is a helper
+    __builtin_amdgcn_s_setprio(0);
+    LIFE_WORK_END();       // lifetime build: the workgroup's stamp ends with its last substep, not with the helper's wait
+    if (!helper) {
+        helper = true;
+        if (tid0 == 0) __hip_atomic_fetch_add(&s.sq_ctl[SPLIT_FINISHED], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
   }
     const int tid = tid0; (void)tid;
 #ifdef HSR_PHASE_TIMING

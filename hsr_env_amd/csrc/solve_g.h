@@ -44,10 +44,12 @@ __device__ __forceinline__ unsigned long long stamp_() {
 #elif defined(HSR_BLOCK_LIFE)
 // second diagnostic build (libhsrsim_life.so, tools/block_life.py): only the (start, end) stamps of every workgroup and the event
 // counters, so the register allocation and the timing of the product kernel are kept
-#define PHASE_T0() unsigned long long dc_[4] = {0, 0, 0, 0}; const unsigned long long r_first_ = __builtin_amdgcn_s_memrealtime()
+#define PHASE_T0() unsigned long long dc_[4] = {0, 0, 0, 0}; unsigned long long r_last_ = 0; const unsigned long long r_first_ = __builtin_amdgcn_s_memrealtime()
+// a workgroup that stays as a helper after its task (persist.h): the end stamp is the end of its last run of substeps
+#define LIFE_WORK_END() do { r_last_ = __builtin_amdgcn_s_memrealtime(); } while (0)
 #define DBGCNT(i, v) do { dc_[i] += (v); } while (0)
 #define PHASE(idx) do {} while (0)
-#define PHASE_FLUSH() do { if (tid == 0 && blockIdx.x < 8192) { unsigned long long *bt_ = s.phase_cyc + 32 + 40 * blockIdx.x; bt_[0] = r_first_; bt_[1] = __builtin_amdgcn_s_memrealtime(); bt_[4] = dc_[0]; bt_[5] = dc_[1]; bt_[6] = dc_[2]; bt_[7] = dc_[3]; } } while (0)
+#define PHASE_FLUSH() do { if (tid == 0 && blockIdx.x < 8192) { unsigned long long *bt_ = s.phase_cyc + 32 + 40 * blockIdx.x; bt_[0] = r_first_; bt_[1] = r_last_ ? r_last_ : __builtin_amdgcn_s_memrealtime(); bt_[4] = dc_[0]; bt_[5] = dc_[1]; bt_[6] = dc_[2]; bt_[7] = dc_[3]; } } while (0)
 // per-env stamps of the lifetime build (batches of up to 8192 envs, behind the records of 4096 workgroups): [0] when the env's env-step was
 // complete (100 MHz clock), [1] the substep at which it was handed over to a solo server (0: never) with the time of the hand-over above bit 16
 #define ENV_STAMP(slot, e, val) do { if ((e) < 8192) s.phase_cyc[32 + 40 * 4096 + 8192 * (slot) + (e)] = (val); } while (0)
@@ -57,6 +59,9 @@ __device__ __forceinline__ unsigned long long stamp_() {
 #define DBGCNT(i, v) do {} while (0)
 #define PHASE(idx) do {} while (0)
 #define PHASE_FLUSH() do {} while (0)
+#endif
+#ifndef LIFE_WORK_END
+#define LIFE_WORK_END() do {} while (0)
 #endif
 // the six spare stamps (26..31): the kinematics stages by default; a timing build with -DHSR_SUBPROF=n moves them inside ONE other phase
 // (1 the MPR section - the old -DHSR_MPR_PROFILE -, 2 the sphere / box culls, 3 box-box, 4 inertia + bias, 5 constraint assembly,

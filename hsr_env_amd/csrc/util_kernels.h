@@ -187,6 +187,12 @@ __global__ void k_queue_init(DevState s, int T, int R) {
     // q_err is NOT cleared here: a trip stays on record until the host has read it (queue_error), however many launches were enqueued since
     if (i < R * T) s.q_items[i] = i < T ? i : -1;
 }
+// a splitting launch (persist.h): control words zeroed, no ticket filled.  q_err is NOT cleared, as above
+__global__ void k_split_init(DevState s) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < SPLIT_CTL_WORDS) s.sq_ctl[i] = 0;
+    for (int k = i; k < s.sq_cap; k += gridDim.x * blockDim.x) s.sq_items[k] = -1;
+}
 // The bitonic network with eight consecutive keys per thread in registers: exchanges at distance 1, 2, 4 stay inside the thread, 8 .. 256 inside
 // the wave (one shuffle per key), and only 512 .. 4096 cross waves through LDS - 10 of the 91 stages need a barrier (round 3: all 91, 124 us of
 // every env-step; the packing it computes saves 280 us of the cfg3 launch)

@@ -90,6 +90,7 @@ PROTOTYPES = {
     "hsr_batch_set_debug": (_int, [_vp, _int]),
     "hsr_batch_set_solo": (_int, [_vp, _int, _float]),
     "hsr_batch_solo_handovers": (_int, [_vp, _ip]),
+    "hsr_batch_set_split": (_int, [_vp, _int, _int, _float, _int, _int]),
     "hsr_batch_set_schedule": (_int, [_vp, _int]),
     "hsr_batch_set_mpr_warm": (_int, [_vp, _int]),
     "hsr_batch_set_queue": (_int, [_vp, _int, _int]),
@@ -527,6 +528,16 @@ class BatchSim:
         out = C.c_int(0)
         _check(self._L, self._L.hsr_batch_solo_handovers(self._b, C.byref(out)))
         return int(out.value)
+
+    def set_split(self, on: bool, period: int = 0, trips: float = -1.0, min_left: int = 0, extra_helpers: int = 0) -> bool:
+        """Hand-over of hard envs inside a launch (include/hsrsim.h): a wave that finds two or more hard envs among its own gives all but
+        the hardest to workgroups that have finished; never changes a result.  period / trips / min_left: 0 / negative / 0 keep the current
+        value; trips = 0 counts every live env as hard and extra_helpers adds workgroups without a task (both for tests).  solo_handovers()
+        counts the hand-overs of the last step.  False when the batch's kernel instance never splits."""
+        rc = self._L.hsr_batch_set_split(self._b, int(on), int(period), float(trips), int(min_left), int(extra_helpers))
+        if rc < 0:
+            _check(self._L, rc)
+        return rc == 0
 
     def set_schedule(self, on: bool):
         """Wave packing of the persistent kernel by env hardness (default on); never changes a result."""

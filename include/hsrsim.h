@@ -191,8 +191,19 @@ int hsr_batch_set_debug(hsr_batch *b, int on);
  * 2048 or more substeps or of more than 2^20 envs run without servers (the hand-over ticket is one int).  Returns 1 (not an error) when the
  * model's kernel instance has no server path. */
 int hsr_batch_set_solo(hsr_batch *b, int servers, float trips);
-/* envs handed over to solo servers by the last persistent launch (synchronises) */
+/* envs handed over by the last persistent launch - to solo servers, or inside a splitting launch (below) (synchronises) */
 int hsr_batch_solo_handovers(hsr_batch *b, int *out);
+/* Hand-over of hard envs inside a launch WITHOUT the work queue (persist.h): a wave advances at the pace of its hardest env, so every
+ * `period` substeps it checks whether two or more of its live envs ran `trips` Newton iterations per substep or more over that window; if so,
+ * and with `min_left` substeps or more ahead, it keeps the hardest and gives the others to workgroups that have already finished their own
+ * task, one env each.  The env runs the ordinary code path there: every result is bit-identical with the split on or off, whoever ran the env
+ * from whichever substep.  Applies to launches of the arm models' constant-configuration kernel instances (cfg3, the cupboard) with wave packing on; any other launch
+ * (queued, more workgroups than the GPU holds at once, 2048 or more substeps, more than 2^20 envs) runs exactly as without it.  on = 0: off (on by default; HSR_SPLIT=0 / 1 override).
+ * period = 0, trips < 0, min_left = 0 keep the current value (defaults 8, 2.5, 40; HSR_SPLIT_PERIOD / _TRIPS / _MIN_LEFT); trips = 0
+ * counts every live env as hard (tests).  extra_helpers (tests; 0 in production) launches that many workgroups without a task which start as
+ * helpers; they must fit next to the tasks' workgroups among those the GPU holds at once, else the launch does not split.  Returns 1 (not an
+ * error) when the batch's kernel instance never splits. */
+int hsr_batch_set_split(hsr_batch *b, int on, int period, float trips, int min_left, int extra_helpers);
 /* wave packing of the persistent kernel (default on; HSR_SCHEDULE=0 turns it off at creation): before every launch the envs are re-distributed over the waves by the
  * Newton iterations they needed at the end of their previous launch (hard envs one per wave, with the easiest as neighbours).
  * A pure scheduling decision: every env's result is bit-identical with it on or off. */
@@ -226,7 +237,8 @@ int hsr_batch_newton_trips(hsr_batch *b, int32_t *out /*[n_envs]*/);
 /* the packing the last persistent launch ran with (k_schedule, csrc/util_kernels.h): out[slot] = env that lane group `slot % (64 / lanes per env)` of task
  * `slot / (64 / lanes per env)` held, -1 = empty; ceil(n_envs / envs per wave) * envs per wave entries.  Contract (tests/test_gpu_hotpath.py): every env exactly
  * once; per chunk of 8192 envs the first lane group of task w holds the env with the w-th most iterations (ties: lower index), the other groups are
- * filled from the easy end.  Results never depend on it. */
+ * filled from the easy end.  Results never depend on it.  An env that its wave handed over inside the launch (hsr_batch_set_split) reads -1: the
+ * table shows the waves as the launch left them. */
 int hsr_batch_packing(hsr_batch *b, int32_t *out /*[ceil(n_envs / epw) * epw]*/);
 
 /* ---- episodes on the device: sampled auto-reset, time limit, episode statistics -------------------------------------------------
