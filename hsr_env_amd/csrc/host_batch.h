@@ -107,10 +107,13 @@ struct hsr_batch {
     std::vector<hsr_replay *> replays;
     // on-policy rollouts (host_rollout.h), likewise
     std::vector<hsr_rollout *> rollouts;
+    // running-moments normalisers (host_normalize.h), likewise
+    std::vector<hsr_norm *> norms;
 };
 static void snap_release_all(hsr_batch *b);     // host_snapshot.h
 static void replay_release_all(hsr_batch *b);   // host_replay.h
 static void rollout_release_all(hsr_batch *b);  // host_rollout.h
+static void norm_release_all(hsr_batch *b);     // host_normalize.h
 template <typename T>
 static int dalloc(hsr_batch *b, T **p, size_t count) {
     void *q = nullptr;

@@ -1,9 +1,9 @@
 """The device loop of ``VecHSREnv(auto_reset=True)``: the torch and device-pointer plumbing around ``BatchSim``'s ``*_dev`` calls.
 
 ``DeviceLoop`` owns the batch's stream as a torch stream, the tensors a step reads and writes, the action-step counter of the device's
-action sampler and the attached ``replay.HindsightReplay`` and ``rollout.OnPolicyRollout`` (either, both or none; they do not know of each
-other).  ``DeviceLoop.step`` is the one place where the order of the library calls of an env-step - step, record, episode end, commit,
-close - is written.  The env keeps the gym surface and the host books.
+action sampler and the attached ``replay.HindsightReplay``, ``rollout.OnPolicyRollout`` and ``normalize.ObsNormalizer`` (any of them or
+none; they do not know of each other).  ``DeviceLoop.step`` is the one place where the order of the library calls of an env-step - step,
+record, episode end, commit, close, observe - is written.  The env keeps the gym surface and the host books.
 
 Importing this module imports torch; ``VecHSREnv`` does so only with ``auto_reset=True``.  There is no CPU stand-in.
 """
@@ -41,7 +41,8 @@ class DeviceLoop:
         self.action_step = 0           # the next draw of sample_action(); part of an env's saved state
         self.replay = None
         self.rollout = None
-        self._buf = None               # the stream and the tensors, made at the first use (and again when a replay or rollout is attached)
+        self.normalizer = None
+        self._buf = None               # the stream and the tensors, made at the first use (and again when something is attached)
 
     def _buffers(self):
         if self._buf is None:
@@ -50,8 +51,10 @@ class DeviceLoop:
                          fret=((n,), f32), done=((n,), u8), kind=((n,), u8), ns=((n,), i32), flen=((n,), i32))
             # rows handed to the replay and the rollout that no other buffer holds: the policy rows (robs: the observation as the env
             # returns it; with the state observation `obs` serves the rollout) and, for the 25-float observation, the terminal rows
-            if self.replay is not None or (self.rollout is not None and self.openai):
+            if self.replay is not None or (self.openai and (self.rollout is not None or self.normalizer is not None)):
                 table.update(robs=((n, self.obs_dim), f32), rmask=((n,), u8))
+            elif self.normalizer is not None:
+                table.update(rmask=((n,), u8))
             if self.rollout is not None and self.openai:
                 table.update(rterm=((n, self.obs_dim), f32))
             device, stream = batch_stream(self.sim)
@@ -101,12 +104,16 @@ class DeviceLoop:
             if replay is not None:
                 replay.record(d["ctrl"], term_rows if openai else d["obs"], d["rew"], d["done"])
             sim.episode_end_dev(ptr["obs"], ptr["rew"], ptr["done"], None if openai else ptr["final"], ptr["kind"], ptr["fret"], ptr["flen"])
-            if openai and fed:
+            if openai and self.normalizer is not None and not fed:
+                policy_rows = d["robs"]                                 # nothing else asked for the policy rows of this observation
+            if openai and (fed or self.normalizer is not None):
                 sim.obs_openai_dev(policy_rows.data_ptr())              # the first observation of the envs that were reset
             if replay is not None:
                 replay.commit(policy_rows, d["kind"])
             if rollout is not None:                                     # after the replay's commit; neither reads what the other wrote
                 rollout.close_step(d["rew"], d["kind"], policy_rows, term_rows)
+            if self.normalizer is not None:                             # the last link: the rows the policy acts on next, counted once
+                self.normalizer.observe(policy_rows)
             host = {k: d[k].cpu().numpy() for k in ("obs", "rew", "done", "ns", "kind", "fret", "flen")}
             if not openai:
                 terminal = d["final"].cpu().numpy()
@@ -117,10 +124,13 @@ class DeviceLoop:
         self.replay = replay
         self._buf = None                                                # the buffers gain the replay's staging rows
 
-    def commit_host_rows(self, obs, mask=None):
+    def commit_host_rows(self, obs, mask=None, count=True):
         """The host rows of a reset() - the observation it returns, and the envs it began an episode for (None: all of them) - go to what the
-        loop feeds: the replay commits them, the rollout begins again from them."""
+        loop feeds: the replay commits them, the rollout begins again from them, the normaliser counts them.  count=False: rows the policy
+        was handed before - make_replay committing the current rows to its new ring, a jump - are not counted a second time."""
         self.begin_rollout(obs)
+        if count:
+            self.observe_host_rows(obs, mask)
         if self.replay is None:
             return
         stream, d = self._buffers()
@@ -133,10 +143,11 @@ class DeviceLoop:
 
     def restart_replay(self, obs):
         """After a jump (load_state, fork) the ring describes a past the envs no longer have: forget it and start from the current rows;
-        so does the rollout."""
+        so does the rollout.  The normaliser's statistics are the learner's and stay as they are."""
         if self.replay is not None:
             self.replay.clear()
-        self.commit_host_rows(obs)
+        self.commit_host_rows(obs, count=False)
+        self.observe_host_rows(obs, count=False)
 
     # ------------------------------------------------------------------ the rollout the loop feeds
     def attach_rollout(self, rollout):
@@ -154,3 +165,29 @@ class DeviceLoop:
             rows.copy_(torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32).reshape(self.n, self.obs_dim)))
             self.rollout.begin(rows)
             stream.synchronize()                                        # the host rows are pageable: the copy must not outlive them
+
+    # ------------------------------------------------------------------ the normaliser the loop feeds
+    def attach_normalizer(self, normalizer):
+        """Nothing the loop already feeds is disturbed: tensors that exist stay, the ones the normaliser needs besides them - the reset mask,
+        and the policy rows of the 25-float observation - are added."""
+        self.normalizer = normalizer
+        if self._buf is not None:
+            stream, d = self._buf
+            table = dict(rmask=((self.n,), torch.uint8), **(dict(robs=((self.n, self.obs_dim), torch.float32)) if self.openai else {}))
+            d.update(zero_tensors(d["ctrl"].device, {k: v for k, v in table.items() if k not in d}))
+
+    def observe_host_rows(self, obs, mask=None, count=True):
+        """The normaliser counts the host rows of a reset() for the envs of `mask` (None: all) and normalises all of them into its
+        ``policy_obs``.  count=False (after a jump): the statistics stay, policy_obs follows the rows."""
+        if self.normalizer is None:
+            return
+        if not count:
+            mask = np.zeros(self.n, dtype=np.uint8)
+        stream, d = self._buffers()
+        rows = d["robs"] if self.openai else d["obs"]
+        with torch.cuda.stream(stream):
+            rows.copy_(torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32).reshape(self.n, self.obs_dim)))
+            if mask is not None:
+                d["rmask"].copy_(torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8).reshape(self.n)))
+            self.normalizer.observe(rows, None if mask is None else d["rmask"])
+            stream.synchronize()                                        # the host rows are pageable: the copies must not outlive them

@@ -291,7 +291,8 @@ class VecHSREnv:
                                  **priority_options)
         self._loop.attach_replay(replay)
         self._get_observation()
-        self._loop.commit_host_rows(self._last_obs)                     # (a rollout begins again too: the loop's tensors were made anew)
+        # (a rollout begins again too: the loop's tensors were made anew.)  Not counted by a normaliser: the policy had these rows before
+        self._loop.commit_host_rows(self._last_obs, count=False)
         return replay
 
     # ------------------------------------------------------------------ on-policy rollouts on the device (rollout.py)
@@ -313,6 +314,29 @@ class VecHSREnv:
         self._get_observation()
         self._loop.begin_rollout(self._last_obs)
         return rollout
+
+    # ------------------------------------------------------------------ observation and goal normalisation on the device (normalize.py)
+    def make_normalizer(self, eps: float = 0.01, clip: float = 5.0):
+        """Attach a normalize.ObsNormalizer to the device loop and return it: running fp64 mean / std of the observation columns
+        (``normalizer.obs``) and of the 3-float goal (``normalizer.goal``) on the device.  Every observation the env hands to the policy
+        is counted exactly once: the current rows of all envs now, the rows of the envs a reset() resets, the rows every step() returns (as
+        the last link of the step, after the replay's commit and the rollout's close).  After each of them ``normalizer.policy_obs``
+        [n_envs, obs_dim] holds the normalised rows on the device for a policy to read without a copy.  What step() and reset() return,
+        and what a replay or rollout stores, stays raw: statistics move, so stored rows are normalised when they are read
+        (``replay.sample(..., normalizer=normalizer)``, ``normalizer.apply_batch``).  Goal statistics come from relabelled samples:
+        ``normalizer.update_goals(batch)``.
+        load_state() and fork() do not change the statistics: they are learner state, not env state (keep them with
+        ``normalizer.state_dict()``); policy_obs follows the rows they jump to."""
+        if self._loop is None:
+            raise ValueError("make_normalizer needs auto_reset=True: the normaliser is fed by the device loop, which only that mode runs")
+        if self._loop.normalizer is not None:
+            raise ValueError("this env already feeds a normaliser")
+        from .normalize import ObsNormalizer
+        normalizer = ObsNormalizer(self.sim, self.obs_dim, eps=eps, clip=clip)
+        self._loop.attach_normalizer(normalizer)
+        self._get_observation()
+        self._loop.observe_host_rows(self._last_obs)
+        return normalizer
 
     # ------------------------------------------------------------------ exact snapshots (sim.Snapshot; DESIGN.md)
     def _no_jump_while_recording(self, what):

@@ -83,12 +83,14 @@ class HindsightReplay:
             torch.div(w, w.max(), out=out["weight"])
         out["sampled_at"] = self._token()
 
-    def sample(self, batch_size: int, beta: float = 0.4) -> dict:
+    def sample(self, batch_size: int, beta: float = 0.4, normalizer=None) -> dict:
         """The next minibatch: obs [B, obs_dim], action [B, nu], next_obs, goal [B, 3], achieved_next [B, 3], reward [B] (float32), done [B]
         (uint8) and index [B, 4] (int32: env, slot, goal slot or -1, relabelled), written on the batch's stream into tensors that the next
         sample() of the same size overwrites.  Order torch work after it with ``torch.cuda.stream(replay.stream)`` or a stream wait.
         A prioritised replay draws by priority and adds prob [B] (priority / total), weight [B] ((count N prob)^-beta over its maximum in the
-        batch) and sampled_at (an int: hand it, or the whole dict, to update_priorities)."""
+        batch) and sampled_at (an int: hand it, or the whole dict, to update_priorities).
+        normalizer (normalize.ObsNormalizer): its ``apply_batch`` normalises the drawn rows in place, in one more launch; the ring keeps
+        raw rows.  None: nothing more runs."""
         b = int(batch_size)
         out = self._buffers.get(b)
         if out is None:
@@ -106,9 +108,11 @@ class HindsightReplay:
             self._replay.sample_dev(self._draw, b, self.her_ratio, p["obs"], p["action"], p["next_obs"], p["goal"], p["achieved_next"], p["reward"],
                                     p["done"], p["index"])
         self._draw = (self._draw + 1) & 0xffffffff
+        if normalizer is not None:
+            normalizer.apply_batch(out)
         return out
 
-    def sample_sequences(self, batch_size: int, seq_len: int, gamma: float = 0.99, beta: float = 0.4) -> dict:
+    def sample_sequences(self, batch_size: int, seq_len: int, gamma: float = 0.99, beta: float = 0.4, normalizer=None) -> dict:
         """The next minibatch as windows of up to `seq_len` steps, for recurrent policies and n-step targets: the sampled step and the
         steps after it inside its episode (never past the episode's end or the ring's newest step), all under one goal - the desired one,
         or the achieved goal of a later step of the episode for a relabelled sample.  With L = seq_len: obs [B, L, obs_dim], action
@@ -119,7 +123,7 @@ class HindsightReplay:
         nstep_done = 0: bootstrap from nstep_obs, target = nstep_return + nstep_discount (1 - nstep_done) V(nstep_obs, goal).
         Tensors are written on the batch's stream and overwritten by the next call of the same (batch_size, seq_len); the draw counter is
         the one sample() advances.  A prioritised replay draws the window's first step by priority and adds prob, weight and sampled_at as
-        sample() does."""
+        sample() does.  normalizer: as in sample(); the padding rows past ``length`` stay zero."""
         b, n = int(batch_size), int(seq_len)
         out = self._seq_buffers.get((b, n))
         if out is None:
@@ -136,6 +140,8 @@ class HindsightReplay:
         else:
             self._replay.sample_seq_dev(self._draw, b, n, self.her_ratio, gamma, ReplaySeqOut(**ptr))
         self._draw = (self._draw + 1) & 0xffffffff
+        if normalizer is not None:
+            normalizer.apply_batch(out)
         return out
 
     def update_priorities(self, batch_or_index, td_error, sampled_at: int = None):

@@ -40,6 +40,7 @@ def raise_if_diverged(sim):
 _vp, _fp_t, _u8p, _i32p = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
 _ip, _ullp = C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)
 _int, _float = C.c_int, C.c_float
+_dp = C.POINTER(C.c_double)
 _RENDER = [_vp, _fp_t, _int, _int, _int, _fp_t]          # batch, camera, track_body, width, height, geom_rgba; then rgb, depth, segid
 # the ABI as this module uses it: name -> (restype, argtypes); include/hsrsim.h declares it (tests/test_abi.py holds the two together)
 PROTOTYPES = {
@@ -146,6 +147,15 @@ PROTOTYPES = {
     "hsr_rollout_stats": (_int, [_vp, _fp_t, _fp_t, _fp_t]),
     "hsr_rollout_minibatch_dev": (_int, [_vp, C.c_uint32, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hsr_rollout_planes_dev": (_int, [_vp, _vp, _vp]),
+    "hsr_batch_norm_create": (_int, [_vp, _int, _float, _float, C.POINTER(_vp)]),
+    "hsr_norm_destroy": (None, [_vp]),
+    "hsr_norm_clear": (_int, [_vp]),
+    "hsr_norm_update_dev": (_int, [_vp, _vp, _int, _vp, _int]),
+    "hsr_norm_apply_dev": (_int, [_vp, _vp, _int, _vp, _int, _int]),
+    "hsr_norm_apply_batch_dev": (_int, [_vp, _vp, _vp, _int, _vp]),
+    "hsr_norm_state": (_int, [_vp, _dp, _dp, _dp, C.POINTER(C.c_uint64)]),
+    "hsr_norm_set_state": (_int, [_vp, C.c_double, _dp, _dp, C.c_uint64]),
+    "hsr_norm_published_dev": (_int, [_vp, _vp, _vp]),
 }
 EXPORTS = list(PROTOTYPES)
 
@@ -286,6 +296,11 @@ class BatchSim:
     def rollout(self, spec: "RolloutSpec") -> "Rollout":
         """A store of `horizon` env-steps on the device with GAE, advantage statistics and shuffled minibatches, bound to this batch."""
         return Rollout(self, spec)
+
+    # -- running-moments normalisers (include/hsrsim.h: hsr_batch_norm_create ..; the class Norm below, normalize.RunningNorm on top of it)
+    def norm(self, dim: int, eps: float = 0.01, clip: float = 5.0) -> "Norm":
+        """Running fp64 moments of `dim` columns on the device with their float32 publish and clipped apply, bound to this batch."""
+        return Norm(self, dim, eps, clip)
 
     def copy_envs(self, src, dst):
         """env dst[i] <- env src[i] on the device, every source read before any destination is written; the destinations then continue
@@ -823,3 +838,56 @@ class Rollout:
     def planes_dev(self, d_adv=None, d_ret=None):
         """The advantage and return planes, float32 [T, N] each (either None)."""
         _check(self.sim._L, self.sim._L.hsr_rollout_planes_dev(self._r, d_adv, d_ret))
+
+
+class NormItem(C.Structure):
+    """include/hsrsim.h: hsr_norm_item."""
+    _fields_ = [("d_rows", C.c_void_p), ("rows", C.c_int64), ("seq_len", C.c_int32), ("which", C.c_int32)]
+
+
+class Norm:
+    """A running-moments normaliser of a batch (include/hsrsim.h: hsr_norm) as the library exposes it: device pointers in, asynchronous on
+    the batch stream.  Its storage is released by close() or by close() of its batch, whichever comes first."""
+
+    def __init__(self, sim: BatchSim, dim: int, eps: float, clip: float):
+        self.sim, self.dim = sim, int(dim)
+        self._r = C.c_void_p()
+        _check(sim._L, sim._L.hsr_batch_norm_create(sim._b, int(dim), float(eps), float(clip), C.byref(self._r)))
+
+    def close(self):
+        if getattr(self, "_r", None):
+            self.sim._L.hsr_norm_destroy(self._r); self._r = None
+
+    __del__ = close
+
+    def clear(self):
+        _check(self.sim._L, self.sim._L.hsr_norm_clear(self._r))
+
+    def update_dev(self, d_rows, stride, d_mask, n):
+        """d_rows float32 [n, dim] with `stride` floats between rows; d_mask uint8 [n] or None."""
+        _check(self.sim._L, self.sim._L.hsr_norm_update_dev(self._r, d_rows, int(stride), d_mask, int(n)))
+
+    def apply_dev(self, d_in, in_stride, d_out, out_stride, n):
+        _check(self.sim._L, self.sim._L.hsr_norm_apply_dev(self._r, d_in, int(in_stride), d_out, int(out_stride), int(n)))
+
+    def state(self):
+        """(count, mean [dim], m2 [dim], skipped) as the device keeps them (fp64; skipped an int); synchronises."""
+        count, skipped = C.c_double(0), C.c_uint64(0)
+        mean, m2 = np.empty(self.dim, np.float64), np.empty(self.dim, np.float64)
+        _check(self.sim._L, self.sim._L.hsr_norm_state(self._r, C.byref(count), mean.ctypes.data_as(_dp), m2.ctypes.data_as(_dp), C.byref(skipped)))
+        return float(count.value), mean, m2, int(skipped.value)
+
+    def set_state(self, count, mean, m2, skipped=0):
+        mean, m2 = (np.ascontiguousarray(a, dtype=np.float64).reshape(self.dim) for a in (mean, m2))
+        _check(self.sim._L, self.sim._L.hsr_norm_set_state(self._r, float(count), mean.ctypes.data_as(_dp), m2.ctypes.data_as(_dp), int(skipped)))
+
+    def published_dev(self, d_mean32=None, d_rstd32=None):
+        """The published float32 vectors, [dim] each, into device arrays (either None)."""
+        _check(self.sim._L, self.sim._L.hsr_norm_published_dev(self._r, d_mean32, d_rstd32))
+
+
+def norm_apply_batch_dev(obs: Norm, goal: Norm, items, d_length=None):
+    """items: (device pointer, rows, seq_len, which: 0 obs / 1 goal) of up to 8 contiguous tensors, normalised in place in one launch."""
+    arr = (NormItem * len(items))(*[NormItem(int(p), int(rows), int(seq), int(which)) for p, rows, seq, which in items])
+    L = (obs or goal).sim._L
+    _check(L, L.hsr_norm_apply_batch_dev(obs._r if obs is not None else None, goal._r if goal is not None else None, arr, len(items), d_length))

@@ -545,6 +545,51 @@ int  hsr_rollout_minibatch_dev(hsr_rollout *r, uint32_t epoch, int first, int co
                                float *d_obs, float *d_act, float *d_logp, float *d_value, float *d_adv, float *d_ret, int32_t *d_index /*[count,2]*/);
 int  hsr_rollout_planes_dev(hsr_rollout *r, float *d_adv, float *d_ret); /* [T,N] copies of the advantage and return planes */
 
+/* ---- running mean / std normalisation of rows on the device: fp64 moments, float32 publish, clipped apply ----
+ * Opt-in; what a learner puts between the env's rows (or a sampled batch) and its networks.  Ownership as for the rollout: a normaliser is
+ * bound to the batch that made it and launches on hsr_batch_stream(); its storage goes with hsr_norm_destroy, or with hsr_batch_destroy of
+ * its batch, whichever is first: after the latter the handle is still the caller's to destroy, and every other use returns HSR_EINVAL.
+ * A batch that never creates one allocates and launches nothing.  A normaliser reads nothing of the batch but the stream, and is NOT part
+ * of an env record: hsr_batch_snapshot_load* / hsr_batch_copy_envs* leave it alone (its statistics are the learner's, not the envs').
+ *
+ * State for dim columns: count (fp64, exact: whole numbers below 2^53), mean[dim] and m2[dim] (fp64), the published float32 mean32[dim]
+ * and rstd32[dim], and skipped (uint64).
+ * update(rows [n, dim] float32 with a row stride in floats, mask uint8 [n] or NULL): a row is selected if its mask byte is non-zero (no
+ *   mask: every row); a selected row counts if all its dim values are finite, else it is left out and adds 1 to skipped (a row the mask
+ *   does not select is neither).  Of the m rows that count: mean_b = sum(x) / m, m2_b = sum((x - mean_b)^2) (a second pass), in fp64, then
+ *   Chan's rule: delta = mean_b - mean; tot = count + m; mean += delta m / tot; m2 += m2_b + delta^2 count m / tot; count = tot.
+ *   m == 0 leaves count, mean, m2 and the published vectors as they were, bit for bit.  Every sum has a shape fixed by (n, dim) alone
+ *   (csrc/normalize.h states it); rows left out add +0.0 in place, so the same rows in the same places give the same bits whatever else
+ *   the array held.  No atomics.
+ * publish, after every update, clear and set_state: std = sqrt(max(m2 / count, eps^2)); mean32 = (float)mean; rstd32 = (float)(1 / std);
+ *   count == 0: mean32 = 0, rstd32 = 1.
+ * apply: y = clamp((x - mean32) rstd32, -clip, clip): a float32 subtraction and a float32 product, each rounded on its own (no fma), then
+ *   y > clip ? clip : y < -clip ? -clip : y, so a NaN stays a NaN.  In place (d_out == d_in with equal strides) or out of place.
+ * apply_batch: up to 8 contiguous tensors of rows in place in ONE launch, each with the statistics of `obs` (which == 0) or `goal`
+ *   (which == 1).  rows = all rows of the tensor; a tensor of windows has seq_len > 1 rows per window, and with d_length [rows / seq_len]
+ *   the rows at and past a window's length are left as they are (padding stays zero).
+ * Every *_dev call is asynchronous on the batch's stream, with one exception: an update whose n is larger than that of every update
+ * before it (the first one included) waits for the stream and allocates its partial sums anew; updates of a size seen before allocate
+ * and wait for nothing.  HSR_EINVAL (nothing launched): dim outside 1..1024; eps <= 0 or not finite;
+ * clip <= 0 or not finite; n < 0; a row stride below dim; set_state with a negative or non-finite count or m2 or a non-finite mean; an
+ * item with rows < 0, seq_len < 1 or rows no multiple of seq_len, or with which outside {0, 1}. */
+typedef struct hsr_norm hsr_norm;
+typedef struct hsr_norm_item {
+    float   *d_rows;          /* [rows, dim of its normaliser], contiguous, normalised in place */
+    int64_t  rows;
+    int32_t  seq_len;         /* 1: plain rows; L: windows of L rows, cut by d_length */
+    int32_t  which;           /* 0: the obs normaliser, 1: the goal normaliser */
+} hsr_norm_item;
+int  hsr_batch_norm_create(hsr_batch *b, int dim, float eps, float clip, hsr_norm **out);
+void hsr_norm_destroy(hsr_norm *r);
+int  hsr_norm_clear(hsr_norm *r);                         /* count = 0, mean = m2 = 0, skipped = 0; publishes the identity */
+int  hsr_norm_update_dev(hsr_norm *r, const float *d_rows, int stride, const uint8_t *d_mask, int n);
+int  hsr_norm_apply_dev(hsr_norm *r, const float *d_in, int in_stride, float *d_out, int out_stride, int n);
+int  hsr_norm_apply_batch_dev(hsr_norm *obs, hsr_norm *goal, const hsr_norm_item *items, int n_items, const int32_t *d_length);
+int  hsr_norm_state(hsr_norm *r, double *count, double *mean /*[dim]*/, double *m2 /*[dim]*/, uint64_t *skipped); /* waits for the stream; each may be NULL */
+int  hsr_norm_set_state(hsr_norm *r, double count, const double *mean, const double *m2, uint64_t skipped);      /* republishes */
+int  hsr_norm_published_dev(hsr_norm *r, float *d_mean32 /*[dim]*/, float *d_rstd32 /*[dim]*/);                    /* either may be NULL */
+
 /* diagnostics (meaningful only in the -DHSR_PHASE_TIMING build, libhsrsim_timing.so; tools/phase_timing.py,
  * tools/block_times.py): per-phase cycle sums of the last launches, and per-workgroup
  * {start, end (s_memrealtime), HW_ID, XCC_ID, Newton trips, sphere-cull candidates, work items, rows} */
