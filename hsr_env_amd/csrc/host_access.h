@@ -74,6 +74,13 @@ extern "C" int hsr_batch_set_split(hsr_batch *b, int on, int period, float trips
     b->split_extra = extra_helpers;
     return b->kernel && b->split_inst ? HSR_OK : 1;      // 1: accepted, but this batch's kernel instance never splits (the setting has no effect)
 }
+extern "C" int hsr_batch_set_split_lone(hsr_batch *b, int on, float trips) {
+    ENTER(b);
+    if (trips > 1000.f) return fail(HSR_EINVAL, "hsr_batch_set_split_lone: trips <= 1000");
+    b->split_lone = on != 0;
+    if (trips > 0.f) b->split_lone_trips = trips;
+    return b->kernel && b->split_inst ? HSR_OK : 1;      // 1: accepted, but this batch's kernel instance never splits (the setting has no effect)
+}
 extern "C" int hsr_batch_solo_handovers(hsr_batch *b, int *out) {
     ENTER_DEV(b);
     if (!out) return fail(HSR_EINVAL, "null argument");

@@ -70,9 +70,11 @@ struct hsr_batch {
     bool split_inst = false;       // the kernel instance is one whose launches may split (host_create.h: kPersistInstances)
     bool split = true;             // on by default: measured on the headline; HSR_SPLIT=0 / hsr_batch_set_split(b, 0, ...) turn it off
     int split_period = 8;          // substeps between two check points of a wave (swept: 8 / 16 / 32)
-    float split_trips = 2.5f;      // an env is hard at this many Newton iterations per substep over the window (swept: 2.5 / 3.5 / 4.5)
+    float split_trips = 2.0f;      // an env is hard at this many Newton iterations per substep over the window (swept: 1.5 / 2.0 / 2.5 / 3.5 / 4.5)
     int split_min_left = 40;       // no hand-over with fewer substeps ahead
     int split_extra = 0;           // tests: workgroups without a task that start as helpers
+    bool split_lone = true;        // the lone rule (split_decide_lone), on by default: measured on the headline; HSR_SPLIT_LONE=0 / hsr_batch_set_split_lone(b, 0, ...) turn it off
+    float split_lone_trips = 4.5f; // a wave's hardest env leaves easier neighbours at this many Newton iterations per substep over the window (swept: 2.5 / 3.5 / 4.5)
     bool kernel_log = false;       // hsr_batch_set_profiling(b, 2): an event pair around every launch of the persistent kernel, no synchronisation
     std::vector<std::pair<hipEvent_t, hipEvent_t>> klog;
     // ray caster (hsr_batch_render*): its own tables and buffers, built on first use; it never touches the simulation state

@@ -17,6 +17,8 @@ static void read_switches(hsr_batch *b) {
     if (atoi(env("HSR_SPLIT_PERIOD")) > 0) b->split_period = atoi(env("HSR_SPLIT_PERIOD"));      // substeps between its check points ...
     if (set("HSR_SPLIT_TRIPS") && atof(env("HSR_SPLIT_TRIPS")) >= 0) b->split_trips = (float)atof(env("HSR_SPLIT_TRIPS"));      // ... its threshold (0: every live env counts as hard) ...
     if (atoi(env("HSR_SPLIT_MIN_LEFT")) > 0) b->split_min_left = atoi(env("HSR_SPLIT_MIN_LEFT"));      // ... and the substeps that must remain
+    if (set("HSR_SPLIT_LONE")) b->split_lone = atoi(env("HSR_SPLIT_LONE")) != 0;  // the lone rule: a lone hard env leaves its easier neighbours (hsr_batch_set_split_lone)
+    if (atof(env("HSR_SPLIT_LONE_TRIPS")) > 0) b->split_lone_trips = (float)atof(env("HSR_SPLIT_LONE_TRIPS"));      // ... and its threshold
     if (set("HSR_QUEUE")) b->queue = atoi(env("HSR_QUEUE")) != 0;                 // work queue forced on / off (hsr_batch_set_queue)
     if (atoi(env("HSR_QUEUE_CHUNK")) > 0) b->queue_chunk = atoi(env("HSR_QUEUE_CHUNK"));         // substeps per round of the work queue ...
     b->queue_chunk_set = atoi(env("HSR_QUEUE_CHUNK")) > 0;                        // ... and no automatic choice then
@@ -378,7 +380,7 @@ static int alloc_state(hsr_batch *b) {
     if ((rc = dalloc(b, &s.sq_items, (size_t)s.sq_cap))) return rc;
     if ((rc = dalloc(b, &s.sq_ctl, SPLIT_CTL_WORDS))) return rc;
     s.solo_servers = 0; s.solo_trips_x4 = 14; s.solo_min_left = 40;
-    s.split_period = 0; s.split_trips_x4 = 14; s.split_min_left = 40;
+    s.split_period = 0; s.split_trips_x4 = 14; s.split_min_left = 40; s.split_lone_x4 = 0;
     s.q_chunk = 0;
     s.slot_env = nullptr;
     return HSR_OK;

@@ -93,7 +93,8 @@ static int launch_persistent(hsr_batch *b, const StepIO &io, int n_substeps, int
         hipLaunchKernelGGL(k_schedule, dim3((b->N + SCHED_CHUNK - 1) / SCHED_CHUNK), dim3(1024), 0, st, b->ds, 64 / b->group, b->d_slot_env);
     const PersistLaunch p = plan_launch(b->N, b->group, b->slots, n_substeps, b->queue, b->queue_chunk, b->queue_chunk_set,
                                         b->solo_servers, b->solo_trips, b->kernel_sv != nullptr, b->schedule,
-                                        SplitSettings{b->split, b->split_inst, b->split_period, b->split_trips, b->split_min_left, b->split_extra});
+                                        SplitSettings{b->split, b->split_inst, b->split_period, b->split_trips, b->split_min_left, b->split_extra,
+                                                      b->split_lone, b->split_lone_trips});
     DevState dsl = b->ds;
     b->handovers_counted = p.rounds > 0 || p.split.on;
     dsl.slot_env = b->schedule ? b->d_slot_env : nullptr;
@@ -105,6 +106,7 @@ static int launch_persistent(hsr_batch *b, const StepIO &io, int n_substeps, int
     }
     if (p.split.on) {
         dsl.split_period = p.split.period; dsl.split_trips_x4 = p.split.trips_x4; dsl.split_min_left = p.split.min_left;
+        dsl.split_lone_x4 = p.split.lone_x4;
         hipLaunchKernelGGL(k_split_init, dim3(8), dim3(256), 0, st, dsl);
     }
     hipEvent_t k0 = nullptr, k1 = nullptr;

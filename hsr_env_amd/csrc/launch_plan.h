@@ -15,7 +15,10 @@ struct PersistLaunch {
     SplitPlan split;               // hard envs handed over inside a launch without the queue (split_logic.h); split.on == 0: none
 };
 // the split settings of a batch, as plan_launch takes them
-struct SplitSettings { bool on, const_instance; int period; float trips; int min_left, extra; };
+struct SplitSettings {
+    bool on, const_instance; int period; float trips; int min_left, extra;
+    bool lone = false; float lone_trips = 4.5f;        // the lone rule (split_decide_lone) and its threshold in Newton iterations per substep
+};
 static inline PersistLaunch plan_launch(int N, int group, int slots, int n_substeps, int queue, int queue_chunk, bool queue_chunk_set,
                                  int solo_servers, float solo_trips, bool has_sv, bool schedule, const SplitSettings &sp) {
     PersistLaunch p{};
@@ -46,5 +49,6 @@ static inline PersistLaunch plan_launch(int N, int group, int slots, int n_subst
     }
     p.split = split_plan(sp.on, group, sp.const_instance, schedule, qon, T, N, slots, n_substeps, sp.period, sp.trips, sp.min_left, sp.extra);
     if (p.split.on) p.grid = T + p.split.extra;
+    if (p.split.on && sp.lone && sp.lone_trips > 0.f && sp.lone_trips <= 1000.f) p.split.lone_x4 = (int)(4.f * sp.lone_trips + 0.5f);
     return p;
 }

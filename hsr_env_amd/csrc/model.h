@@ -97,6 +97,9 @@ struct DevState {
     // substeps or more ahead, gives all but the hardest to workgroups that have finished.  split_period == 0: off.  It reuses sq_items / sq_ctl
     // (eight control words: persist.h SPLIT_*), which are idle in such a launch
     int split_period, split_trips_x4, split_min_left;
+    // the lone rule (split_decide_lone): the hardest env a wave would keep goes to a helper too if it ran split_lone_x4 / 4 iterations per
+    // substep or more while a neighbour that stays ran fewer.  0: off
+    int split_lone_x4;
     unsigned long long *capstat;     // [4] cap statistics (include/hsrsim.h: hsr_batch_cap_counts)
     unsigned long long *phase_cyc;   // diagnostic build only (HSR_PHASE_TIMING): per-phase cycle sums
 };

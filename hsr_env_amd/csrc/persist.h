@@ -104,7 +104,9 @@ __device__ __forceinline__ void q_push(const DevState &s, int T, int task, int r
 // A wave advances at the pace of its hardest env per substep, so two hard envs in one wave cost more than either alone; which envs are
 // hard shows only while the launch runs.  From the moment the first workgroups finish, their wave slots are idle: a workgroup that has
 // finished its own task becomes a HELPER, and a wave that finds two or more hard envs among its own at a check point (split_decide) keeps
-// the hardest and gives the others to helpers, one each.  A helper runs the env through the ordinary code path - lane group 0 of a task
+// the hardest and gives the others to helpers, one each.  With the lone rule (DevState::split_lone_x4 > 0, split_decide_lone) a wave whose
+// hardest env still has easier live neighbours gives that env away as well and goes on with the neighbours: even the easiest neighbours cost
+// a hard env several per cent, a helper's wave costs nothing.  A helper runs the env through the ordinary code path - lane group 0 of a task
 // row of its own in the env -> slot table, the other groups out of range - so the env's results are the same bit for bit whoever runs it.
 // sq_ctl (zeroed in front of the launch by k_split_init, which also empties sq_items):
 //   [SPLIT_CLAIMED]   tickets taken by helpers          [SPLIT_RESERVED]  tickets reserved by donors (= hand-overs of the launch)
@@ -382,8 +384,8 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
         // gets issue priority over the wave it shares its SIMD with, which has slack
         if (sub - sub0 >= 4 && 2 * trips_acc > 5 * (sub - sub0)) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);      // A/B on the bench: +4 %
         // ---------------- check point of a splitting launch: every split_period substeps the wave asks whether two or more of its envs were
-        // hard over the window; if so, and if helpers are free, it keeps the hardest and ends this run here (wave-uniform; lane 0 touches
-        // global memory only when the decision says "donate")
+        // hard over the window - or, the lone rule, whether its one hard env still has easier live neighbours; if so, and if helpers are
+        // free, it gives envs away and ends this run here (wave-uniform; lane 0 touches global memory only when the decision says "donate")
         if constexpr (SPLIT_INST && !SOLO) {
             if (sub == split_check) {
                 split_check += s.split_period;
@@ -395,7 +397,7 @@ __global__ void __launch_bounds__(64, 2) k_env_step_mf(const DevModel *__restric
                 unsigned alive = 0;
 #pragma unroll
                 for (int j = 0; j < EPB; j++) alive |= (unsigned)((ab >> (j * G)) & 1ull) << j;
-                const unsigned want = split_decide(wt, alive, EPB, sub, n_substeps - sub, s.split_period, s.split_trips_x4, s.split_min_left);
+                const unsigned want = split_decide_lone(wt, alive, EPB, sub, n_substeps - sub, s.split_period, s.split_trips_x4, s.split_min_left, s.split_lone_x4);
                 if (want) {
                     give = split_acquire(s, want);
                     if (give) sub_stop = sub;

@@ -92,6 +92,7 @@ PROTOTYPES = {
     "hsr_batch_set_solo": (_int, [_vp, _int, _float]),
     "hsr_batch_solo_handovers": (_int, [_vp, _ip]),
     "hsr_batch_set_split": (_int, [_vp, _int, _int, _float, _int, _int]),
+    "hsr_batch_set_split_lone": (_int, [_vp, _int, _float]),
     "hsr_batch_set_schedule": (_int, [_vp, _int]),
     "hsr_batch_set_mpr_warm": (_int, [_vp, _int]),
     "hsr_batch_set_queue": (_int, [_vp, _int, _int]),
@@ -550,6 +551,16 @@ class BatchSim:
         value; trips = 0 counts every live env as hard and extra_helpers adds workgroups without a task (both for tests).  solo_handovers()
         counts the hand-overs of the last step.  False when the batch's kernel instance never splits."""
         rc = self._L.hsr_batch_set_split(self._b, int(on), int(period), float(trips), int(min_left), int(extra_helpers))
+        if rc < 0:
+            _check(self._L, rc)
+        return rc == 0
+
+    def set_split_lone(self, on: bool, trips: float = -1.0) -> bool:
+        """The lone rule of the hand-over inside a launch (include/hsrsim.h): a wave whose hardest env ran `trips` Newton iterations per
+        substep or more, next to a live env that ran fewer, gives that env to a finished workgroup too and goes on with the easier ones;
+        never changes a result.  Needs set_split on; trips <= 0 keeps the current threshold.  False when the batch's kernel instance
+        never splits."""
+        rc = self._L.hsr_batch_set_split_lone(self._b, int(on), float(trips))
         if rc < 0:
             _check(self._L, rc)
         return rc == 0

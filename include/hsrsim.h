@@ -199,11 +199,18 @@ int hsr_batch_solo_handovers(hsr_batch *b, int *out);
  * task, one env each.  The env runs the ordinary code path there: every result is bit-identical with the split on or off, whoever ran the env
  * from whichever substep.  Applies to launches of the arm models' constant-configuration kernel instances (cfg3, the cupboard) with wave packing on; any other launch
  * (queued, more workgroups than the GPU holds at once, 2048 or more substeps, more than 2^20 envs) runs exactly as without it.  on = 0: off (on by default; HSR_SPLIT=0 / 1 override).
- * period = 0, trips < 0, min_left = 0 keep the current value (defaults 8, 2.5, 40; HSR_SPLIT_PERIOD / _TRIPS / _MIN_LEFT); trips = 0
+ * period = 0, trips < 0, min_left = 0 keep the current value (defaults 8, 2.0, 40; HSR_SPLIT_PERIOD / _TRIPS / _MIN_LEFT); trips = 0
  * counts every live env as hard (tests).  extra_helpers (tests; 0 in production) launches that many workgroups without a task which start as
  * helpers; they must fit next to the tasks' workgroups among those the GPU holds at once, else the launch does not split.  Returns 1 (not an
  * error) when the batch's kernel instance never splits. */
 int hsr_batch_set_split(hsr_batch *b, int on, int period, float trips, int min_left, int extra_helpers);
+/* The lone rule of a splitting launch (split_logic.h: split_decide_lone): even the easiest neighbours cost a hard env several per cent of its
+ * wave's pace, so at a check point a wave whose hardest remaining env ran `trips` Newton iterations per substep or more over the window, while a
+ * live env that stays ran fewer, gives that env to a helper as well and goes on with the easier ones.  A wave whose live envs are all at or above
+ * the threshold keeps its hardest, and a wave never gives away its last live env.  Same launches, period, min_left and helpers as
+ * hsr_batch_set_split, which must be on; results stay bit-identical.  on = 0: off (on by default, measured: DESIGN.md; HSR_SPLIT_LONE=0 / 1 override);
+ * trips <= 0 keeps the current threshold (default 4.5; HSR_SPLIT_LONE_TRIPS).  Returns 1 (not an error) when the batch's kernel instance never splits. */
+int hsr_batch_set_split_lone(hsr_batch *b, int on, float trips);
 /* wave packing of the persistent kernel (default on; HSR_SCHEDULE=0 turns it off at creation): before every launch the envs are re-distributed over the waves by the
  * Newton iterations they needed at the end of their previous launch (hard envs one per wave, with the easiest as neighbours).
  * A pure scheduling decision: every env's result is bit-identical with it on or off. */
