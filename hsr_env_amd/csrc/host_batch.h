@@ -111,11 +111,14 @@ struct hsr_batch {
     std::vector<hsr_rollout *> rollouts;
     // running-moments normalisers (host_normalize.h), likewise
     std::vector<hsr_norm *> norms;
+    // cross-entropy-method planners (host_plan.h), likewise
+    std::vector<hsr_plan *> plans;
 };
 static void snap_release_all(hsr_batch *b);     // host_snapshot.h
 static void replay_release_all(hsr_batch *b);   // host_replay.h
 static void rollout_release_all(hsr_batch *b);  // host_rollout.h
 static void norm_release_all(hsr_batch *b);     // host_normalize.h
+static void plan_release_all(hsr_batch *b);     // host_plan.h
 template <typename T>
 static int dalloc(hsr_batch *b, T **p, size_t count) {
     void *q = nullptr;

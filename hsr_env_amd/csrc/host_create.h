@@ -455,6 +455,7 @@ extern "C" void hsr_batch_destroy(hsr_batch *b) {
     replay_release_all(b);
     rollout_release_all(b);
     norm_release_all(b);
+    plan_release_all(b);
     for (void *p : b->allocs) hipFree(p);
     if (b->d_rimg) hipFree(b->d_rimg);
     if (b->d_cap) hipFree(b->d_cap);

@@ -32,6 +32,7 @@
 #include "replay_prio.h"
 #include "rollout.h"
 #include "normalize.h"
+#include "plan.h"
 #include "cfg_consts.h"
 
 #include "host_model.h"      // error message, blob loader, hsr_model_*, hull planes: plain C++, no HIP
@@ -47,3 +48,4 @@
 #include "host_replay.h"     // hindsight replay: the transition ring and its sampler (kernels: replay.h, replay_prio.h; books and checks: replay_logic.h, replay_prio_logic.h)
 #include "host_rollout.h"    // on-policy rollouts: store, GAE, statistics, shuffled minibatches (kernels: rollout.h; books and checks: rollout_logic.h)
 #include "host_normalize.h"  // running mean / std normalisation of rows: fp64 moments, publish, apply (kernels: normalize.h; arithmetic and checks: normalize_logic.h)
+#include "host_plan.h"       // cross-entropy-method planner over forked envs: draws, costs, rank and refit (kernels: plan.h; arithmetic and checks: plan_logic.h)

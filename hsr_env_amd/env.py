@@ -338,6 +338,20 @@ class VecHSREnv:
         self._loop.observe_host_rows(self._last_obs)
         return normalizer
 
+    # ------------------------------------------------------------------ planning on the device (planner.py)
+    def make_planner(self, samples: int = 64, horizon: int = 3, **options):
+        """A planner.CEMPlanner for this env: ``planner.plan()`` returns the action to take now in every env, a torch tensor on the device
+        that step() takes as it is with auto_reset=True (``.cpu().numpy()`` without).  It forks every env `samples` times into a batch of
+        its own, plays sampled action sequences of `horizon` env-steps there and refits; this env is only read, through a snapshot, and
+        behaves bit for bit as without a planner.  Nothing is attached to the env: call ``plan()`` when an action is wanted, with
+        ``fresh=`` the envs whose episode just began.  options: iterations, elites, gamma, alpha, init_std, min_std, seed (None: the
+        env's) of planner.CEMPlanner; a shard passes its env_offset on.  Needs a goal with a body and a point (ValueError otherwise) and a
+        simulator handle with snapshots (BatchSim)."""
+        if not hasattr(self.sim, "snapshot"):
+            raise NotImplementedError("make_planner needs a simulator handle with snapshots (BatchSim): the candidates are exact forks")
+        from .planner import CEMPlanner
+        return CEMPlanner(self, samples, horizon, **options)
+
     # ------------------------------------------------------------------ exact snapshots (sim.Snapshot; DESIGN.md)
     def _no_jump_while_recording(self, what):
         if self._recorder is not None:

@@ -157,6 +157,20 @@ PROTOTYPES = {
     "hsr_norm_state": (_int, [_vp, _dp, _dp, _dp, C.POINTER(C.c_uint64)]),
     "hsr_norm_set_state": (_int, [_vp, C.c_double, _dp, _dp, C.c_uint64]),
     "hsr_norm_published_dev": (_int, [_vp, _vp, _vp]),
+    "hsr_batch_plan_create": (_int, [_vp, _vp, C.POINTER(_vp)]),
+    "hsr_plan_destroy": (None, [_vp]),
+    "hsr_plan_reset_dev": (_int, [_vp, _vp]),
+    "hsr_plan_shift_dev": (_int, [_vp, _vp]),
+    "hsr_plan_begin_dev": (_int, [_vp]),
+    "hsr_plan_sample_dev": (_int, [_vp, C.c_uint32, _int, _int, _vp]),
+    "hsr_plan_accumulate_dev": (_int, [_vp, _int]),
+    "hsr_plan_add_cost_dev": (_int, [_vp, _vp]),
+    "hsr_plan_update_dev": (_int, [_vp]),
+    "hsr_plan_action_dev": (_int, [_vp, _vp]),
+    "hsr_plan_costs_dev": (_int, [_vp, _vp, _vp]),
+    "hsr_plan_state_dev": (_int, [_vp, _vp, _vp]),
+    "hsr_plan_best_dev": (_int, [_vp, _vp, _vp]),
+    "hsr_plan_failed": (_int, [_vp, C.POINTER(C.c_uint32)]),
 }
 EXPORTS = list(PROTOTYPES)
 
@@ -302,6 +316,11 @@ class BatchSim:
     def norm(self, dim: int, eps: float = 0.01, clip: float = 5.0) -> "Norm":
         """Running fp64 moments of `dim` columns on the device with their float32 publish and clipped apply, bound to this batch."""
         return Norm(self, dim, eps, clip)
+
+    # -- cross-entropy-method planners (include/hsrsim.h: hsr_batch_plan_create ..; the class Plan below, planner.CEMPlanner on top of it)
+    def plan(self, spec: "PlanSpec") -> "Plan":
+        """A CEM planner whose candidates are this batch's envs (groups x samples of them), bound to this batch."""
+        return Plan(self, spec)
 
     def copy_envs(self, src, dst):
         """env dst[i] <- env src[i] on the device, every source read before any destination is written; the destinations then continue
@@ -895,6 +914,76 @@ class Norm:
     def published_dev(self, d_mean32=None, d_rstd32=None):
         """The published float32 vectors, [dim] each, into device arrays (either None)."""
         _check(self.sim._L, self.sim._L.hsr_norm_published_dev(self._r, d_mean32, d_rstd32))
+
+
+class PlanSpec(C.Structure):
+    """include/hsrsim.h: hsr_plan_spec."""
+    _fields_ = [("seed", C.c_uint64), ("env_offset", C.c_uint32), ("groups", C.c_int32), ("samples", C.c_int32), ("horizon", C.c_int32),
+                ("elites", C.c_int32), ("goal_body", C.c_int32), ("geofence", C.c_float), ("gamma", C.c_float), ("alpha", C.c_float),
+                ("init_std", C.c_float), ("min_std", C.c_float)]
+
+
+class Plan:
+    """The CEM planner of a planning batch (include/hsrsim.h: hsr_plan) as the library exposes it: device pointers in, asynchronous on the
+    batch stream.  Its storage is released by close() or by close() of its batch, whichever comes first."""
+
+    def __init__(self, sim: BatchSim, spec: PlanSpec):
+        self.sim, self.spec = sim, spec
+        self._r = C.c_void_p()
+        _check(sim._L, sim._L.hsr_batch_plan_create(sim._b, C.byref(spec), C.byref(self._r)))
+
+    def close(self):
+        if getattr(self, "_r", None):
+            self.sim._L.hsr_plan_destroy(self._r); self._r = None
+
+    __del__ = close
+
+    def reset_dev(self, d_mask=None):
+        """The groups with d_mask[p] != 0 (uint8 [P]; None: all): mean <- 0 clamped into the ctrl range, sigma <- init_std half_range."""
+        _check(self.sim._L, self.sim._L.hsr_plan_reset_dev(self._r, d_mask))
+
+    def shift_dev(self, d_mask=None):
+        """The masked groups: mean[h] <- mean[h + 1], the last step repeats; sigma back to its initial value."""
+        _check(self.sim._L, self.sim._L.hsr_plan_shift_dev(self._r, d_mask))
+
+    def begin_dev(self):
+        _check(self.sim._L, self.sim._L.hsr_plan_begin_dev(self._r))
+
+    def sample_dev(self, call, iteration, h, d_ctrl):
+        """d_ctrl float32 [N, nu]: the candidates' actions of step h, iteration `iteration` (0..255) of plan call `call`."""
+        _check(self.sim._L, self.sim._L.hsr_plan_sample_dev(self._r, int(call) & 0xffffffff, int(iteration), int(h), d_ctrl))
+
+    def accumulate_dev(self, h):
+        """After step_dev of step h: the candidates' costs take the step's distance to the goal."""
+        _check(self.sim._L, self.sim._L.hsr_plan_accumulate_dev(self._r, int(h)))
+
+    def add_cost_dev(self, d_extra):
+        _check(self.sim._L, self.sim._L.hsr_plan_add_cost_dev(self._r, d_extra))
+
+    def update_dev(self):
+        _check(self.sim._L, self.sim._L.hsr_plan_update_dev(self._r))
+
+    def action_dev(self, d_ctrl):
+        """d_ctrl float32 [P, nu] <- mean[p][0]."""
+        _check(self.sim._L, self.sim._L.hsr_plan_action_dev(self._r, d_ctrl))
+
+    def costs_dev(self, d_cost=None, d_reach_step=None):
+        """J float32 [N] and reach_step int32 [N] into device arrays (either None)."""
+        _check(self.sim._L, self.sim._L.hsr_plan_costs_dev(self._r, d_cost, d_reach_step))
+
+    def state_dev(self, d_mean=None, d_sigma=None):
+        """mean and sigma, float32 [P, H, nu] each, into device arrays (either None)."""
+        _check(self.sim._L, self.sim._L.hsr_plan_state_dev(self._r, d_mean, d_sigma))
+
+    def best_dev(self, d_index=None, d_cost=None):
+        """Index int32 [P] and cost float32 [P] of every group's best candidate of the last update (either None)."""
+        _check(self.sim._L, self.sim._L.hsr_plan_best_dev(self._r, d_index, d_cost))
+
+    def failed(self):
+        """Updates of every group that found no finite cost, uint32 [P]; synchronises."""
+        out = np.empty(self.spec.groups, np.uint32)
+        _check(self.sim._L, self.sim._L.hsr_plan_failed(self._r, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
 
 
 def norm_apply_batch_dev(obs: Norm, goal: Norm, items, d_length=None):

@@ -597,6 +597,85 @@ int  hsr_norm_state(hsr_norm *r, double *count, double *mean /*[dim]*/, double *
 int  hsr_norm_set_state(hsr_norm *r, double count, const double *mean, const double *m2, uint64_t skipped);      /* republishes */
 int  hsr_norm_published_dev(hsr_norm *r, float *d_mean32 /*[dim]*/, float *d_rstd32 /*[dim]*/);                    /* either may be NULL */
 
+/* ---- planning on the device: a cross-entropy-method (CEM) controller over forked envs ----
+ * Opt-in.  The simulator is the model: fork the current state K times (hsr_batch_snapshot_save_dev / _load_dev above), try K action
+ * sequences over H env-steps, keep the good ones, refit, repeat.  A planner works on a PLANNING batch, a second batch of the same model on
+ * the same device with N = P K envs: it plans for P acting envs ("groups") with K candidates each, candidate k of group p = env p K + k.
+ * The acting batch is never touched by a planner; it is only read, by the caller, through a snapshot.  Ownership as for the replay and the
+ * normaliser: a planner is bound to the (planning) batch that made it and launches on hsr_batch_stream(); its storage goes with
+ * hsr_plan_destroy, or with hsr_batch_destroy of its batch, whichever is first: after the latter the handle is still the caller's to destroy,
+ * and every other use returns HSR_EINVAL.  A batch that never creates one allocates and launches nothing.  Not part of an env record.
+ *
+ * State: mean, sigma float32 [P][H][nu]; per candidate the cost J and the discount g (float32), alive (u8), reach_step (int32, -1 = the
+ * goal was not reached); per group failed (u32: updates that found no finite cost) and the index and cost of the best candidate of the
+ * last update.  The actions as sampled are kept, float32 [P][H][nu][K], for the refit.  A new planner is reset and begun.
+ * The range of actuator a: (lo, hi) = its ctrlrange, a side without a limit (not finite, or the compiled models' marker 1e30) counts as
+ * -1 / +1, the convention of hsr_batch_sample_ctrl_dev; half_range = (hi - lo) 0.5, a float32 difference and a float32 product.
+ *   reset(d_mask [P] or NULL = all): mean <- clamp(0, lo, hi), sigma <- init_std half_range (a float32 product), for the masked groups.
+ *   shift(d_mask or NULL): mean[h] <- mean[h + 1], the last step repeats; sigma <- its initial value as in reset.
+ *   begin: J = 0, g = 1, alive = 1, reach_step = -1 for every candidate; once per iteration, after the candidates were loaded.
+ *   sample(call, iter, h, d_ctrl [N][nu]): ctrl = clamp(mean[p][h][a] + sigma[p][h][a] z, lo, hi), a float32 product and a float32 sum each
+ *     rounded on its own, clamp(x) = x < lo ? lo : x > hi ? hi : x.  Candidate 0 takes z = 0: the current mean is always a candidate.
+ *     Otherwise z is the Irwin-Hall normal of ONE Philox block (no logf / cosf: bit-reproducible): u_i = (w_i >> 8) 2^-24,
+ *     z = (((u0 + u1) + (u2 + u3)) - 2) (float)sqrt(3), every operation a float32 operation of its own; |z| <= 2 sqrt(3).
+ *     Key (seed & 0xffffffff, seed >> 32), counter (env_offset + p, call 256 + iter, 7, (k H + h) nu + a): stream 7.  iter is in 0..255.
+ *   accumulate(h), after hsr_batch_step_dev of step h, for a live candidate, every operation a float32 operation of its own:
+ *     d = sqrt((dx dx + dy dy) + dz dz) of xpos(goal_body) - mocap_pos (xpos as hsr_batch_body_xpos gives it; an IEEE square root).  This is
+ *     the expression of the env-step's goal test without its contractions and with an exact square root, so the two distances may differ in
+ *     the last bit; `done` is the step's own.  If the env is bad (hsr_batch_bad_state): J = +inf, alive = 0.  Else J = J + g d, then
+ *     g = g gamma, and if the step latched done: alive = 0, reach_step = h - the rest of the horizon costs nothing.
+ *   add_cost(d_extra [N]): J = J + extra for every candidate; the hook for a learned terminal value.
+ *   update, one workgroup per group: key = J, a NaN or an infinity of either sign counting as +inf (by the bits).
+ *     rank(k) = #{ j : key_j < key_k or (key_j == key_k and j < k) }; E' = min(elites, number of finite costs); k is elite iff rank(k) < E'.
+ *     best index = the candidate of rank 0, best cost = its key (candidate 0 and +inf when no cost is finite).
+ *     E' == 0: mean and sigma stay bit for bit, failed += 1.  Otherwise per (h, a), over the actions x as sampled, in fp64:
+ *       m = (sum over elites of x) / E';  v = (sum over elites of (x - m)^2) / E' (a second pass; the difference and the square each rounded);
+ *       mean <- (float)(mean + alpha (m - mean));  sigma <- (float)max(sigma + alpha (sqrt(v) - sigma), min_std half_range[a]), every
+ *       operation a double operation of its own (alpha, min_std, half_range, mean, sigma widened exactly).
+ *     Both sums run over all K leaves, candidate k at leaf k, a non-elite adding +0.0 in place, in a tree whose shape depends on K only:
+ *       lane l of 64 adds the leaves l, l + 64, l + 128, .. serially from 0.0 in this order; then the 64 lane values are added in the tree
+ *       v[l] += v[l + off] for off = 32, 16, 8, 4, 2, 1, the sum being lane 0's.  A chain is at most ceil(K / 64) + 6 additions long.
+ *   action(d_ctrl [P][nu]): mean[p][0].
+ *   readers: costs (J [N], reach_step [N]), state (mean, sigma), best (index [P], cost [P]) copy on the stream, each output may be NULL;
+ *     failed copies to the host and waits for the stream.
+ * All _dev calls are asynchronous on the planning batch's stream.  No atomics anywhere.  HSR_EINVAL, nothing launched and everything as it
+ * was: create with a NULL argument, a model without actuators, samples outside 2..1024, envs != groups samples, horizon outside 1..64,
+ * elites outside 1..samples, a goal_body out of range or the mocap body, a batch with extra goal terms (hsr_batch_set_goals with n > 0: a
+ * cost of several terms cannot be computed from one goal point; accumulate refuses likewise when terms were set later), gamma outside
+ * [0, 1], alpha outside (0, 1], init_std or min_std not finite or <= 0, samples horizon nu >= 2^32; sample with iter outside 0..255, h
+ * outside 0..H-1 or a NULL d_ctrl; accumulate with h outside 0..H-1; add_cost, action, failed with a NULL array.
+ * geofence is what the caller hands to hsr_batch_step_dev of the planning batch: it is part of the spec for the layers above, the
+ * library neither checks nor reads it. */
+typedef struct hsr_plan hsr_plan;
+typedef struct hsr_plan_spec {
+    uint64_t seed;
+    uint32_t env_offset;      /* as in hsr_episode_spec: global id of group 0, so a shard draws what the single batch draws for the same envs */
+    int32_t  groups;          /* P */
+    int32_t  samples;         /* K */
+    int32_t  horizon;         /* H */
+    int32_t  elites;
+    int32_t  goal_body;
+    float    geofence;
+    float    gamma;
+    float    alpha;
+    float    init_std;
+    float    min_std;
+} hsr_plan_spec;
+int  hsr_batch_plan_create(hsr_batch *b, const hsr_plan_spec *spec, hsr_plan **out);
+void hsr_plan_destroy(hsr_plan *r);
+int  hsr_plan_reset_dev(hsr_plan *r, const uint8_t *d_mask);
+int  hsr_plan_shift_dev(hsr_plan *r, const uint8_t *d_mask);
+int  hsr_plan_begin_dev(hsr_plan *r);
+int  hsr_plan_sample_dev(hsr_plan *r, uint32_t call, int iter, int h, float *d_ctrl);
+int  hsr_plan_accumulate_dev(hsr_plan *r, int h);
+int  hsr_plan_add_cost_dev(hsr_plan *r, const float *d_extra);
+int  hsr_plan_update_dev(hsr_plan *r);
+int  hsr_plan_action_dev(hsr_plan *r, float *d_ctrl);
+int  hsr_plan_costs_dev(hsr_plan *r, float *d_cost /*[N]*/, int32_t *d_reach_step /*[N]*/);
+int  hsr_plan_state_dev(hsr_plan *r, float *d_mean /*[P,H,nu]*/, float *d_sigma /*[P,H,nu]*/);
+int  hsr_plan_best_dev(hsr_plan *r, int32_t *d_index /*[P]*/, float *d_cost /*[P]*/);
+int  hsr_plan_failed(hsr_plan *r, uint32_t *failed /*[P]*/);
+
 /* diagnostics (meaningful only in the -DHSR_PHASE_TIMING build, libhsrsim_timing.so; tools/phase_timing.py,
  * tools/block_times.py): per-phase cycle sums of the last launches, and per-workgroup
  * {start, end (s_memrealtime), HW_ID, XCC_ID, Newton trips, sphere-cull candidates, work items, rows} */
